@@ -1,7 +1,17 @@
 """Contrastive pre-training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c5] [--no-cpu-baseline]
-                    [--augment host|device|subgraph|mix]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c5]
+                    [--augment host|device|subgraph|mix] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-kernel-timing]]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line
+(metric, value, ms_per_step = wall time of the timed region / K, the median
+step, the configuration, the last loss).  --dump-outputs DIR then also writes
+what the last timed step left -- loss, flat gradient, parameters, BatchNorm
+running statistics -- as DIR/<name>.npy (float32); inputs and initial weights
+are seeded, so two builds run with the same arguments compare array by array.
+--full adds the measurements listed under "With --full" below, all taken after
+the timed region (and after the dump).
 
 A step is the reference's hot-loop iteration (molclr.py:108-128): two
 encoder forwards of augmented views, F.normalize, NT-Xent, backward, Adam —
@@ -18,7 +28,10 @@ graphs.  Both views run through one paired encoder pass with per-view
 BatchNorm statistics (the reference's two calls).  N > 1 runs under torchrun,
 one rank per GPU over RCCL: the NT-Xent batch is global (512 N), weak scaling.
 
-The JSON line adds:
+With --full the JSON line adds (null in a plain run):
+  host_enqueue_ms_per_step — the host's enqueue time of one step from an idle
+                  device, median of three extra steps.
+  parity        — CapturedTrainStep.replay_vs_eager on one of the run's batches.
   roofline      — the GIN scatter-add (molclr_gine_aggregate_fwd; GCN's
                   molclr_gcn_aggregate_fwd for c3), HBM-bound:
                   algorithmic bytes per launch / mean kernel duration in the
@@ -106,7 +119,19 @@ def parse():
                    help="run every step eagerly (host-enqueued launches) instead of replaying "
                         "the HIP graph captured per batch-size bucket (molclr_amd.graph_step; "
                         "paired pass only; N > 1 captures the RCCL collectives too)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region, also measure what the headline figure does not "
+                        "need: the host enqueue time, the kernel rooflines (extra eager steps), "
+                        "the replay-vs-eager parity check, the c4 NT-Xent roofline and the CPU "
+                        "baseline (--no-kernel-timing / --no-cpu-baseline / --mfma-steps trim it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (its "
+                        "loss, the flat gradient, the parameters and BatchNorm running "
+                        "statistics it left) as DIR/<name>.npy, float32")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def log(rank, *a):
@@ -384,22 +409,15 @@ def main():
     for i in range(args.warmup):
         loss = step(i)
     torch.cuda.synchronize()
-    log(rank, f"warm-up done, loss {loss.item():.4f}")
-    # host cost of one step: enqueue time starting from an idle device (extra,
-    # untimed steps; if it approaches ms_per_step the step is launch-bound)
-    host = []
-    for i in range(3):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        step(args.warmup + args.steps + i)
-        host.append(time.perf_counter() - t0)
-    torch.cuda.synchronize()
+    if args.warmup:
+        log(rank, f"warm-up done, loss {loss.item():.4f}")
 
-    # the timed region carries dispatch events on the scatter-add launches only
-    # (10 per step); timing every GEMM launch too costs ~13 % of the step.  A
-    # replayed graph cannot carry them: the scatter-add is then timed over
-    # extra eager steps after the timed region, like the GEMMs
-    timer = None if args.no_kernel_timing or captured is not None else \
+    # --full, eager steps: the timed region carries dispatch events on the
+    # scatter-add launches only (10 per step); timing every GEMM launch too
+    # costs ~13 % of the step.  A replayed graph cannot carry them: the
+    # scatter-add is then timed over extra eager steps after the timed region,
+    # like the GEMMs
+    timer = None if not args.full or args.no_kernel_timing or captured is not None else \
         ops.KernelTimer(kinds=(agg_kind,))
     ops.set_kernel_timer(timer)
     if world > 1:
@@ -442,10 +460,29 @@ def main():
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     median_ms = statistics.median(step_ms)
 
+    if args.dump_outputs and rank == 0:
+        # before any further step: the state the last timed step left
+        stats = [b.reshape(-1).float() for n, b in model.named_buffers()
+                 if n.endswith(("running_mean", "running_var"))]
+        dump_outputs(Path(args.dump_outputs), {
+            "loss": loss.detach().reshape(1), "grad": opt.flat_grad, "params": opt.flat,
+            **({"bn_running_stats": torch.cat(stats)} if stats else {})})
+
+    # --full: host cost of one step, the enqueue time starting from an idle
+    # device (extra, untimed steps; if it approaches ms_per_step the step is
+    # launch-bound)
+    host = []
+    for i in range(3 if args.full else 0):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step(args.warmup + args.steps + i)
+        host.append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+
     # (the library keeps one timer: read the scatter-add samples before the GEMM pass)
     s = timer.summary() if timer is not None else {}
     agg_timing = "hipExtLaunchKernelGGL dispatch events in the timed region"
-    if captured is not None and not args.no_kernel_timing and args.mfma_steps > 0:
+    if args.full and captured is not None and not args.no_kernel_timing and args.mfma_steps > 0:
         timer = ops.KernelTimer(kinds=(agg_kind,))
         ops.set_kernel_timer(timer)
         for i in range(args.mfma_steps):
@@ -532,7 +569,7 @@ def main():
     # the run's batches (outside the timed region): the replay
     # over its capacity bucket (padding rows) vs the batch at its own size
     parity = None
-    if captured is not None:
+    if args.full and captured is not None:
         parity = captured.replay_vs_eager(*views_of(args.warmup))  # a prepared batch
         parity = {kk: (round(v, 9) if isinstance(v, float) else
                        [v[0], round(v[1], 9)] if isinstance(v, list) else v)
@@ -545,11 +582,11 @@ def main():
             1e-4 if precision == "bf16" else 1e-5) and parity["running_stats_rel"] <= 1e-6)
 
     roofline_ntxent_c4 = None
-    if rank == 0 and not args.no_kernel_timing and precision != "bf16":
+    if args.full and rank == 0 and not args.no_kernel_timing and precision != "bf16":
         roofline_ntxent_c4 = ntxent_c4_roofline(dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log(rank, "timing the CPU baseline (oracle) ...")
         # c5's oracle step (fp32, 2B = 2048 broadcast cosine) takes tens of
         # seconds: one timed step after the warm-up bounds the sample
@@ -582,7 +619,8 @@ def main():
                                    if args.augment == "device" else
                                    f"device: molclr_aug_views ({args.augment}) inside the step")},
             "final_loss": round(final_loss, 5),
-            "host_enqueue_ms_per_step": round(statistics.median(host) * 1e3, 3),
+            "full": args.full,
+            "host_enqueue_ms_per_step": round(statistics.median(host) * 1e3, 3) if host else None,
             "captures": captured.captures if captured is not None else 0,
             "captures_in_timed_region": captures_timed,
             "ranks": per_rank,
@@ -658,6 +696,27 @@ def ntxent_c4_roofline(dev, reps: int = 20) -> dict:
             "frac_of_fp32_mfma_peak": round(tfs / FP32_MFMA_PEAK_TFS, 4), "traffic": None,
             "rows": n, "cols": 2 * B, "dim": C, "us_per_step": round(us, 1),
             "timing": f"HIP events around {reps} fwd+bwd pairs, standalone, after the timed region"}
+
+
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir: Path, tensors: dict) -> None:
+    """--dump-outputs: every tensor as out_dir/<name>.npy, float32.  The whole
+    dump stays within DUMP_BUDGET_BYTES: if it would not, a tensor over its
+    equal share of the budget is stored as a fixed sample of its elements
+    (seed 0, ascending positions), the same positions in every run of the
+    same shapes."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    fits = 4 * sum(t.numel() for t in tensors.values()) <= DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // max(len(tensors), 1) // 4  # float32 elements per tensor
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if not fits and a.size > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
 
 
 def load_pmc_traffic(config: str, two_pass: bool):

@@ -15,22 +15,22 @@ Run in the build container (where /root/reference exists):
   BatchNorm statistics of the checkpoint) and stores ``h`` [16, 512] and
   ``out`` [16, 256].
 
-Output: ``gcn_pretrained_b16.npz`` (the state dict as float32 arrays under
-``w/<key>``, the batch, and the fp64 outputs), about 4 MB.  The fixture is
-data: the checkpoint's tensors and the oracle's outputs.
+Output: ``gcn_pretrained_b16.part<k>.npz`` (the state dict as float32 arrays
+under ``w/<key>``, the batch, and the fp64 outputs), about 4 MB over several
+files of less than 1 MiB each (tests/golden_parts.py writes and reads them).
+The fixture is data: the checkpoint's tensors and the oracle's outputs.
 """
 from __future__ import annotations
 
 import sys
 from pathlib import Path
 
-import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 REF_CKPT = Path("/root/reference/ckpt/pretrained_gcn/checkpoints/model.pth")
-OUT = Path(__file__).resolve().parent / "gcn_pretrained_b16.npz"
+OUT = Path(__file__).resolve().parent / "gcn_pretrained_b16"
 
 
 def main():
@@ -47,8 +47,10 @@ def main():
     arrays.update(x=xi.x.numpy(), edge_index=xi.edge_index.numpy(),
                   edge_attr=xi.edge_attr.numpy(), batch=xi.batch.numpy(),
                   h=h.numpy(), out=out.numpy())
-    np.savez_compressed(OUT, **arrays)
-    print(f"wrote {OUT} ({OUT.stat().st_size / 1e6:.1f} MB): atoms {xi.x.shape[0]}, "
+    from tests.golden_parts import save_parts
+    files = save_parts(OUT, arrays)
+    print(f"wrote {len(files)} files {OUT.name}.part*.npz "
+          f"({sum(f.stat().st_size for f in files) / 1e6:.1f} MB): atoms {xi.x.shape[0]}, "
           f"edges {xi.edge_index.shape[1]}, |h| {h.norm():.4f}, |out| {out.norm():.4f}")
 
 

@@ -49,6 +49,9 @@ def _inputs():
 def _worker(rank, port, out_q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    # this test is about the CPU path: on a host with GPUs the ranks must not
+    # see them (set before this process first asks for a device)
+    os.environ.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     from molclr_amd import distributed as mdist
     r, w, dev = mdist.init(backend="gloo")
     assert (r, w, dev.type) == (rank, WORLD, "cpu")

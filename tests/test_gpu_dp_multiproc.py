@@ -43,7 +43,8 @@ def test_dp_step_two_ranks():
 
 def test_bench_two_ranks():
     r = _torchrun([str(ROOT / "bench.py"), "--gpus", "2", "--config", "c1", "--steps", "4",
-                   "--warmup", "2", "--batches", "2", "--no-cpu-baseline", "--mfma-steps", "1"], 240)
+                   "--warmup", "2", "--batches", "2", "--full", "--no-cpu-baseline",
+                   "--mfma-steps", "1"], 240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 prints the one JSON line

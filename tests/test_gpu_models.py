@@ -507,18 +507,18 @@ def test_any_emb_dim(dev, kind, L, D, B, pool):
 
 def test_gcn_pretrained_checkpoint_eval_matches_oracle(dev):
     """SURVEY §8(c) golden (3): the reference's own trained GCN
-    (ckpt/pretrained_gcn, 5 x 300, feat 512; tests/golden/gcn_pretrained_b16.npz,
+    (ckpt/pretrained_gcn, 5 x 300, feat 512; tests/golden/gcn_pretrained_b16.part*.npz,
     made by tests/golden/make_gcn_pretrained.py and pinned to the shipped file
     by tests/test_oracle_golden.py) loaded strictly into the HIP GCN, eval mode
     (the checkpoint's running BatchNorm statistics), one fixed 16-molecule
     batch: h and out within 1e-5 norm-wise of the fp64 oracle
     (models/gcn_molclr.py:94-158)."""
-    import numpy as np
-
     from molclr_amd.data import Batch
     from molclr_amd.gcn_molclr import GCN
-    d = np.load(GOLDEN / "gcn_pretrained_b16.npz")
-    sd = {k[2:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("w/")}
+
+    from .golden_parts import load_parts
+    d = load_parts(GOLDEN / "gcn_pretrained_b16")
+    sd = {k[2:]: torch.from_numpy(d[k]) for k in d if k.startswith("w/")}
     model = GCN(5, 300, 512)
     model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()

@@ -10,6 +10,7 @@ from oracle import ntxent_math
 from oracle.reference_cpu import RefGCN, RefGINet, RefNTXentLoss
 
 from .conftest import GOLDEN
+from .golden_parts import load_parts
 
 CASES = sorted(GOLDEN.glob("ntxent_*.npz"))
 
@@ -97,14 +98,13 @@ def test_trainable_param_counts():
 
 
 def _gcn_fixture():
-    import numpy as np
-    d = np.load(GOLDEN / "gcn_pretrained_b16.npz")  # allow_pickle=False (default)
-    sd = {k[2:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("w/")}
+    d = load_parts(GOLDEN / "gcn_pretrained_b16")
+    sd = {k[2:]: torch.from_numpy(d[k]) for k in d if k.startswith("w/")}
     return d, sd
 
 
 def test_gcn_pretrained_fixture_is_the_shipped_checkpoint():
-    """tests/golden/gcn_pretrained_b16.npz carries the reference's shipped
+    """tests/golden/gcn_pretrained_b16.part*.npz carry the reference's shipped
     pretrained_gcn weights (ckpt/pretrained_gcn/checkpoints/model.pth):
     every key / shape of the manifest, the manifest's sha256 of five tensors."""
     import hashlib
@@ -116,7 +116,16 @@ def test_gcn_pretrained_fixture_is_the_shipped_checkpoint():
 
 
 def test_gcn_pretrained_fixture_oracle_outputs():
-    """The fixture's h / out are the fp64 oracle's (eval mode) on its batch."""
+    """The fixture's h / out are the fp64 oracle's (eval mode) on its batch.
+
+    Held to 1e-12 norm-wise, not bit for bit: the host's BLAS picks its fp64
+    summation order by CPU and thread count (one thread instead of eight
+    already changes the last bits), so equality held only on the host that
+    wrote the fixture.  fp64 rounds at 1.1e-16; a dot product of K <= 512
+    terms through 5 layers and 3 head products is bounded by about
+    8 * 512 * 1.1e-16 = 4.5e-13 in the worst case, so a correct oracle on any
+    host lies within 1e-12 and nothing coarser than rounding passes
+    (the HIP model's own bound against the same fixture is 1e-5)."""
     from molclr_amd.data import Batch
     from oracle.reference_cpu import RefGCN
     d, sd = _gcn_fixture()
@@ -127,4 +136,7 @@ def test_gcn_pretrained_fixture_oracle_outputs():
               edge_attr=torch.from_numpy(d["edge_attr"]), batch=torch.from_numpy(d["batch"]))
     with torch.no_grad():
         h, out = ref(b)
-    assert torch.equal(h, torch.from_numpy(d["h"])) and torch.equal(out, torch.from_numpy(d["out"]))
+    assert h.dtype == out.dtype == torch.float64
+    eh, eo = _rel(h.numpy(), d["h"]), _rel(out.numpy(), d["out"])
+    print(f"oracle vs fixture: h {eh:.2e}, out {eo:.2e}")
+    assert eh <= 1e-12 and eo <= 1e-12, (eh, eo)

@@ -2,7 +2,6 @@
 restatements of the reference semantics (models/ginet_molclr.py,
 models/gcn_molclr.py, PyG 1.6.3 propagate / add_self_loops / mean pool)."""
 import numpy as np
-import pytest
 import torch
 
 from oracle.reference_cpu import (RefGCNConv, RefGINEConv, RefGINet, global_max_pool,
@@ -118,12 +117,15 @@ def test_ginet_forward_shapes_and_batch_independence():
 
 
 def test_pretrained_checkpoint_loads_into_product_gcn():
-    from pathlib import Path
-    p = Path("/root/reference/ckpt/pretrained_gcn/checkpoints/model.pth")
-    if not p.exists():
-        pytest.skip("reference checkpoint not mounted (build container only)")
+    """The reference's shipped pretrained_gcn state dict (its tensors as stored
+    in tests/golden/gcn_pretrained_b16.part*.npz, pinned to the shipped file by
+    tests/test_oracle_golden.py) loads strictly into the product GCN."""
     from molclr_amd.gcn_molclr import GCN
-    sd = torch.load(p, map_location="cpu", weights_only=True)
+
+    from .conftest import GOLDEN
+    from .golden_parts import load_parts
+    d = load_parts(GOLDEN / "gcn_pretrained_b16")
+    sd = {k[2:]: torch.from_numpy(v) for k, v in d.items() if k.startswith("w/")}
     m = GCN(num_layer=5, emb_dim=300, feat_dim=512)
     res = m.load_state_dict(sd, strict=True)
     assert not res.missing_keys and not res.unexpected_keys
