@@ -492,7 +492,10 @@ int molclr_gemm_f32_h3(const float* A, const float* amax, int a_row_parts, const
  * MOLCLR_ERR_UNSUPPORTED otherwise).  Kernels 1 and 2 give bit-identical C,
  * bits and maxima; 3 (16 x 16 x 32 MFMAs) sums each product's k in another
  * order, equal to fp32 rounding.  The row maxima (crow) are
- * molclr_gemm_row_parts(N) arrays whatever the kernel. */
+ * molclr_gemm_row_parts(N) arrays whatever the kernel.  The bs kernels read
+ * three wave words of per-wave-pair row maxima, so a product with
+ * -a_row_parts > 129 (a row may span four waves, e.g. K = 600) is not theirs:
+ * the automatic choice runs it on pp / q6, impl 2 / 3 answer UNSUPPORTED. */
 int molclr_gemm_f32_h3_impl(const float* A, const float* amax, int a_row_parts,
                             const uint16_t* hplanes, float* C, int64_t M, int64_t N, int64_t K,
                             int64_t lda, int64_t ldc, int epilogue_flags, const float* bias,

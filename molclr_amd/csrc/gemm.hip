@@ -3154,12 +3154,23 @@ int dispatch_q6_tn(int epi, const Args& a, int64_t npad, hipStream_t s) {
 // <= 8 partial arrays or per-wave pairs.  MOLCLR_GEMM_BS=0 keeps pp / q6;
 // g_bs_force (molclr_gemm_f32_h3_impl): 1 never, 2 bs, 3 bs16.
 int g_bs_force = 0;
+// Per-wave pairs (arow_parts < 0, d4 = -arow_parts float4s per row): k_gemm_bs
+// and k_gemm_bsn read three wave words per row.  A row of d4 units starting
+// at unit u of a wave touches ceil((u + d4) / 64) waves, at most three for
+// every u <= 63 iff d4 <= 129; a longer row can span four, whose last
+// maximum would be missed and the row shifted too far (fp16 overflow).  Such
+// products go to pp / q6, whose row_max_of_waves walks all of a row's waves.
+bool bs_row_scales_ok(const Args& a, int h3) {
+  if (h3 != 2) return true;
+  if (a.arow_parts > 8) return false;
+  return a.arow_parts >= 0 || (-a.arow_parts >= 64 && -a.arow_parts <= 129);
+}
 bool bs_shape_ok(const Args& a, int64_t npad, int epi, int h3) {
   if (h3 == 0 || a.N <= 320 || a.K <= 288 || a.K > 304 || a.ldb != 320) return false;
   if (a.lda % 4 || a.ldc % 4 || a.N % 4 || (reinterpret_cast<uintptr_t>(a.C) & 15)) return false;
   if (a.M * a.lda * 4 >= (1ll << 31) || 2 * npad * a.ldb * 2 >= (1ll << 31)) return false;
   if (epi == MOLCLR_EPI_RELU_MASK && a.bits_in == nullptr) return false;
-  if (h3 == 2 && (a.arow_parts > 8 || (a.arow_parts < 0 && -a.arow_parts < 64))) return false;
+  if (!bs_row_scales_ok(a, h3)) return false;
   return true;
 }
 bool use_bs(const Args& a, int64_t npad, int epi, int h3) {
@@ -3238,7 +3249,7 @@ bool use_bs64(const Args& a, int64_t npad, int epi, int h3) {
   if (a.lda % 4 || a.ldc % 4 || a.N % 4 || (reinterpret_cast<uintptr_t>(a.C) & 15)) return false;
   if (a.M * a.lda * 4 >= (1ll << 31) || 2 * npad * a.ldb * 2 >= (1ll << 31)) return false;
   if (epi == MOLCLR_EPI_RELU_MASK && a.bits_in == nullptr) return false;
-  if (h3 == 2 && (a.arow_parts > 8 || (a.arow_parts < 0 && -a.arow_parts < 64))) return false;
+  if (!bs_row_scales_ok(a, h3)) return false;  // K = 600 pairs (d4 = 150): four waves per row
   return true;
 }
 template <int EPI, int H3>

@@ -8,7 +8,13 @@ Kernel level, each against float64 on the same bf16-rounded inputs:
   on the same (bf16-representable) values and rounded to bf16 (same fp32 adds,
   one rounding);
 * segmented BatchNorm in bf16 storage: statistics within 1e-5, outputs within
-  bf16 rounding.
+  bf16 rounding;
+* the kernels that do arithmetic and then store bf16 (the products, BatchNorm
+  forward and backward) held to CORRECT rounding by tests/rounding.py
+  (test_*_rounding): every element in the window of one round-to-nearest-even
+  of the fp32-accumulated result, at most 0.5 % of them off RNE_bf16(fp64
+  result), no rounding bias -- which truncation, rounding twice or one wrong
+  tail path miss, and the norm-wise 2^-8 above does not.
 Model level: GINet(precision='bf16') against the fp64 oracle of the reference
 (oracle/reference_cpu.py) -- the stated bf16 tolerances (BF16_TOL) below."""
 import copy
@@ -20,6 +26,8 @@ import torch
 from molclr_amd import _lib, ops
 from molclr_amd.data import DeviceGraph
 from molclr_amd.dataset import SyntheticPairBatches
+
+from . import rounding as R
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -271,6 +279,141 @@ def test_batchnorm_bf16_segments(dev):
         assert rel(sm[s], zf[r0:r0 + r].double().mean(0)) < TOL
         r0 += r
     assert rel(rm, rm_ref) < TOL and rel(rv, rv_ref) < TOL
+
+
+def _figures(what, rep):
+    """The figures behind check_bf16_rounded, one line per checked output (pytest -s)."""
+    print(f"rounding {what}: share_off={rep['share_off']:.3e} mean_d={rep['mean_d']:+.5f} "
+          f"(bound {rep['bias_bound']:.5f}, n={rep['n_bias']}) outside={rep['outside_window']}")
+
+
+_QB_IMPLS = (-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9)  # as test_gemm_bf16
+
+
+@pytest.mark.parametrize("M,N,K", R.SHAPES)
+def test_gemm_bf16_rounding(dev, M, N, K):
+    """molclr_gemm_bf16: every epilogue and the K-major weight operand, through
+    EVERY tile shape (each impl against the fp64 reference, not against impl
+    -1), rounds the fp32-accumulated result once, to nearest even.  Shapes:
+    partial row and column tiles, K off the K step, one small tile."""
+    from molclr_amd._lib import EPI_BIAS, EPI_BIAS_RELU, EPI_NONE, EPI_RELU_MASK
+    lib = _lib.load()
+    A, W, Wt, b, aux = R.gemm_case(M, N, K)
+    Ad, bd, auxd = bf(A).to(dev), b.to(dev), bf(aux).to(dev)
+    planes = ops.weight_planes(W.to(dev), N, K, K, 0)    # plane 0 = W (bf16-valued already)
+    planes_t = ops.weight_planes(Wt.to(dev), N, K, N, 1)
+    y, mag = R.gemm_ref(A, W)
+    yb, magb = R.gemm_ref(A, W, b)
+    keep = (aux > 0).double()
+    # a ReLU clamps the reference: an element whose window straddles 0 may be 0
+    # or the rounded value, both inside [RNE(ref - e), RNE(ref + e)]
+    cases = {EPI_NONE: (y, mag), EPI_BIAS: (yb, magb), EPI_BIAS_RELU: (yb.clamp(min=0), magb),
+             EPI_RELU_MASK: (y * keep, mag * keep)}
+    yt, magt = R.gemm_ref(A, Wt.t())
+    for impl in _QB_IMPLS:
+        for epi, (ref, m) in cases.items():
+            C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+            assert lib.molclr_gemm_bf16_impl(Ad.data_ptr(), planes.data_ptr(), C.data_ptr(), M, N,
+                                             K, K, N, epi, bd.data_ptr(), auxd.data_ptr(), N, None,
+                                             impl) == 0, lib.molclr_last_error()
+            what = f"gemm_bf16 {M}x{N}x{K} impl {impl} epi {epi}"
+            _figures(what, R.check_bf16_rounded(C, ref, m, R.GEMM_SLACK, what=what))
+        C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+        assert lib.molclr_gemm_bf16_impl(Ad.data_ptr(), planes_t.data_ptr(), C.data_ptr(), M, N, K,
+                                         K, N, EPI_NONE, None, None, 0, None, impl) == 0
+        what = f"gemm_bf16 {M}x{N}x{K} impl {impl} K-major"
+        _figures(what, R.check_bf16_rounded(C, yt, magt, R.GEMM_SLACK, what=what))
+    # the plain entry point is the automatic choice
+    C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+    assert lib.molclr_gemm_bf16(Ad.data_ptr(), planes.data_ptr(), C.data_ptr(), M, N, K, K, N,
+                                EPI_BIAS, bd.data_ptr(), None, 0, None) == 0
+    R.check_bf16_rounded(C, yb, magb, R.GEMM_SLACK, what="gemm_bf16 plain")
+
+
+@pytest.mark.parametrize("M,N,K", [s for s in R.SHAPES if s[2] % 64 == 0])  # the entry's K % 64
+def test_gemm_bf16_bits_rounding(dev, M, N, K):
+    """molclr_gemm_bf16_bits: the bias+ReLU output and the product masked by
+    its bits are once-rounded results; the bits equal C > 0."""
+    from molclr_amd._lib import EPI_BIAS_RELU, EPI_RELU_MASK
+    lib = _lib.load()
+    A, W, Wt, b, _ = R.gemm_case(M, N, K)
+    dz = R.gemm_case(M, N, K, seed=M + N + K + 1)[0]
+    planes = ops.weight_planes(W.to(dev), N, K, K, 0)
+    planes_t = ops.weight_planes(Wt.to(dev), N, K, N, 1)
+    Ad, dzd, bd = bf(A).to(dev), bf(dz).to(dev), b.to(dev)
+    nw = (N + 31) // 32
+    bits = torch.full((nw, M), -1, dtype=torch.int32, device=dev)
+    C1 = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+    assert lib.molclr_gemm_bf16_bits(Ad.data_ptr(), planes.data_ptr(), C1.data_ptr(), M, N, K, K, N,
+                                     EPI_BIAS_RELU, bd.data_ptr(), bits.data_ptr(), None, None) == 0
+    yb, magb = R.gemm_ref(A, W, b)
+    what = f"gemm_bf16_bits {M}x{N}x{K} bias+relu"
+    _figures(what, R.check_bf16_rounded(C1, yb.clamp(min=0), magb, R.GEMM_SLACK, what=what))
+    pos = torch.zeros(M, nw * 32, dtype=torch.bool, device=dev)
+    pos[:, :N] = C1.float() > 0
+    w = (pos.view(M, nw, 32).long() << torch.arange(32, device=dev)).sum(2)  # [M, nw]
+    want = w.t().contiguous().to(torch.int64) & 0xFFFFFFFF
+    assert torch.equal(bits.to(torch.int64) & 0xFFFFFFFF, want)
+    D1 = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
+    assert lib.molclr_gemm_bf16_bits(dzd.data_ptr(), planes_t.data_ptr(), D1.data_ptr(), M, N, K, K,
+                                     N, EPI_RELU_MASK, None, None, bits.data_ptr(), None) == 0
+    keep = (C1.float() > 0).double().cpu()  # the mask the bits hold (checked above)
+    yt, magt = R.gemm_ref(dz, Wt.t())
+    what = f"gemm_bf16_bits {M}x{N}x{K} mask from bits"
+    _figures(what, R.check_bf16_rounded(D1, yt * keep, magt * keep, R.GEMM_SLACK, what=what))
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("rows,D", R.BN_CASES)
+def test_batchnorm_bf16_rounding(dev, rows, D, relu):
+    """Segmented BatchNorm in bf16 storage against fp64 on the same bf16
+    inputs: the forward's y and the backward's dz once-rounded (dz had no fp64
+    comparison before), dgamma / dbeta within 1e-5.  Magnitude sums (the
+    absolute values of the terms of the fp64 formulas; rounding.bn_fwd_ref /
+    bn_bwd_ref):
+        y  = gamma (z - mean) invstd + beta
+        mag_y  = |gamma| invstd (|z| + |mean|) + |beta|
+        dz = gamma invstd (g - mean_rows(g) - xhat mean_rows(g xhat)),  g = dy [y > 0]
+        mag_dz = |gamma| invstd (|g| + mean_rows|g| + X mean_rows(|g| X)),
+                 X = (|z| + |mean|) invstd.
+    The backward's ReLU mask is the kernels' own y > 0 (fp64 autograd through
+    BatchNorm times that constant mask); it may differ from the fp64 y > 0
+    only where the forward's window straddles 0."""
+    import ctypes
+    lib = _lib.load()
+    n = sum(rows)
+    z, dy, gamma, beta = R.bn_case(rows, D)
+    zd, dyd, gd, bd = bf(z).to(dev), bf(dy).to(dev), gamma.to(dev), beta.to(dev)
+    seg = (ctypes.c_int64 * len(rows))(*rows)
+    wsb = lib.molclr_batchnorm_seg_workspace_bytes(len(rows), seg, D)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rm, rv = torch.zeros(D, device=dev), torch.ones(D, device=dev)
+    y = torch.full((n, D), float("nan"), dtype=torch.bfloat16, device=dev)
+    sm, si = torch.empty(len(rows), D, device=dev), torch.empty(len(rows), D, device=dev)
+    assert lib.molclr_batchnorm_seg_fwd(zd.data_ptr(), gd.data_ptr(), bd.data_ptr(), rm.data_ptr(),
+                                        rv.data_ptr(), None, y.data_ptr(), sm.data_ptr(),
+                                        si.data_ptr(), len(rows), seg, D, _lib.DTYPE_BF16, 0.1, 1e-5,
+                                        1, relu, ws.data_ptr(), wsb, None) == 0
+    y64, mag, mean64, inv64 = R.bn_fwd_ref(z, gamma, beta, rows)
+    assert rel(sm, mean64) < TOL and rel(si, inv64) < TOL
+    what = f"batchnorm fwd rows {rows} D {D} relu {relu}"
+    _figures(what, R.check_bf16_rounded(y, y64.clamp(min=0) if relu else y64, mag,
+                                        R.BN_FWD_SLACK, what=what))
+    mask = None
+    if relu:
+        mask = (y.float() > 0).cpu()
+        flipped = mask != (y64 > 0)
+        assert bool((y64.abs()[flipped] <= R.BN_FWD_SLACK * R.U32 * mag[flipped]).all())
+    dz = torch.full((n, D), float("nan"), dtype=torch.bfloat16, device=dev)
+    dg, db = torch.empty(D, device=dev), torch.empty(D, device=dev)
+    assert lib.molclr_batchnorm_seg_bwd(dyd.data_ptr(), zd.data_ptr(), gd.data_ptr(), bd.data_ptr(),
+                                        sm.data_ptr(), si.data_ptr(), dz.data_ptr(), dg.data_ptr(),
+                                        db.data_ptr(), len(rows), seg, D, _lib.DTYPE_BF16, relu, 0,
+                                        ws.data_ptr(), wsb, None) == 0
+    dz64, dg64, db64, bmag = R.bn_bwd_ref(z, dy, gamma, beta, rows, mask)
+    what = f"batchnorm bwd rows {rows} D {D} relu {relu}"
+    _figures(what, R.check_bf16_rounded(dz, dz64, bmag, R.BN_BWD_SLACK, what=what))
+    assert rel(dg, dg64) < TOL and rel(db, db64) < TOL
 
 
 def _models(L, D, F, seed):

@@ -1353,19 +1353,43 @@ def test_gemm_h3_bs16(dev, M, N, K, scales, epi, acc):
     assert err.max().item() < 2e-6 if scales != "tensor" else rel(Cc, ref) < 2e-6
 
 
-@pytest.mark.parametrize("M,N,K", [(30556, 300, 600), (1000, 256, 580), (70, 300, 600),
-                                   (4099, 320, 608)])
-@pytest.mark.parametrize("scales", ["tensor", "rows"])
+# every shape with per-tensor and per-row scales; per-wave pairs at the two
+# small shapes (the pairs are built on the host)
+_BS64_CASES = ([(M, N, K, sc) for sc in ("tensor", "rows")
+                for M, N, K in [(30556, 300, 600), (1000, 256, 580), (70, 300, 600),
+                                (4099, 320, 608)]]
+               + [(70, 300, 600, "pairs"), (1000, 256, 580, "pairs")])
+
+
+@pytest.mark.parametrize("M,N,K,scales", _BS64_CASES,
+                         ids=[f"{sc}-{M}-{N}-{K}" for M, N, K, sc in _BS64_CASES])
 @pytest.mark.parametrize("epi,acc", [(0, 0), (1, 1), (2, 0), (3, 0)])
 def test_gemm_h3_bs64(dev, M, N, K, scales, epi, acc):
     """The K = 600 products (lin2, dagg) on k_gemm_bsn with 64-column tiles
     (molclr_gemm_f32_h3_impl 3, 19 whole-K steps, an odd count): C against
     fp64 at the h3 kernels' accuracy, max |C| and max |A| consistent with it,
-    every epilogue (ReLU mask from bits), accumulation, partial tiles."""
+    every epilogue (ReLU mask from bits), accumulation, partial tiles.
+
+    "pairs": A's row maxima as per-wave pairs.  At K = 600 / 580 a row is 150
+    / 145 float4s and, starting late in a wave, spans FOUR waves, while
+    k_gemm_bsn reads three wave words per row; every such row here carries
+    its largest magnitude, >= 2^10 times the rest of the row, in its last
+    float4, so a kernel that drops the fourth wave's maximum shifts the row
+    2^10 too far (fp16 overflow) and C misses the row-wise bound.  The
+    library refuses these products to the bs kernels (-a_row_parts > 129;
+    impl 3 answers "does not take this product"), so the pairs cases run the
+    automatic choice, impl 0, which must reach a kernel that walks all of a
+    row's waves."""
     from molclr_amd import _lib
     lib = _lib.load()
     g = torch.Generator().manual_seed(M + N + K + epi + 2)
     A = torch.randn(M, K, generator=g) * torch.pow(10.0, -6 * torch.rand(M, 1, generator=g))
+    if scales == "pairs":
+        d4 = K // 4
+        s0 = torch.arange(M) * d4
+        four = ((s0 + d4 - 1) // 64 - s0 // 64) == 3
+        assert four.sum() >= M // 5  # the rows that start at unit >= 193 - d4 of a wave
+        A[four, K - 1] = A[four, :K - 4].abs().amax(1) * 2048.0
     W = (torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5
     bias = torch.randn(N, generator=g) * 0.1
     mask = torch.rand(M, N, generator=g) > 0.4
@@ -1381,8 +1405,10 @@ def test_gemm_h3_bs64(dev, M, N, K, scales, epi, acc):
         amax, parts = torch.zeros(2048, device=dev), 0
         assert lib.molclr_absmax_f32(Ad.data_ptr(), M, K, K, amax.data_ptr(), 0,
                                      ops._stream(Ad)) == 0
-    else:
+    elif scales == "rows":
         amax, parts = Ad.abs().amax(1).contiguous(), 1
+    else:
+        amax, parts = _wave_pairs(A).to(dev), -(K // 4)
     C0 = torch.randn(M, N, generator=g).to(dev)
     C = C0.clone()
     cmax = torch.zeros(2048, device=dev)
@@ -1391,7 +1417,7 @@ def test_gemm_h3_bs64(dev, M, N, K, scales, epi, acc):
         Ad.data_ptr(), amax.data_ptr(), parts, planes.data_ptr(), C.data_ptr(), M, N, K, K, N,
         epi | (_lib.EPI_ACCUMULATE if acc else 0), bd.data_ptr(), None, 0,
         mb.data_ptr() if epi == 3 else None, cmax.data_ptr(), None, aout.data_ptr(), None,
-        ops._stream(Ad), 3)
+        ops._stream(Ad), 0 if scales == "pairs" else 3)
     assert rc == 0, lib.molclr_last_error()
     torch.cuda.synchronize()
     assert cmax.max().item() == C.abs().max().item()
