@@ -305,6 +305,28 @@ int molclr_gine_aggregate_fwd_rowmax(const float* x, const int32_t* rowptr, cons
                                      const uint8_t* ecode, const uint32_t* nbr, const float* Ec,
                                      float* out, int64_t N, int64_t D, float* rowparts,
                                      float* slot, molclr_stream_t stream);
+/* GINE aggregation whose source is a BatchNorm output that is never stored:
+ * z [N,D] is the BatchNorm INPUT and coeffs its apply coefficients (scale
+ * [nseg,D], then shift [nseg,D]; molclr_batchnorm_seg_coeffs; 16-byte
+ * aligned).  Every source element, the self row's and the gathered rows', is
+ * read as y = fma(z, scale, shift), then max(y, 0) when relu -- the
+ * arithmetic of molclr_batchnorm_seg_fwd's apply (bf16: y rounded to bf16 as
+ * the apply stores it) -- so out is bit-identical to molclr_batchnorm_seg_fwd
+ * followed by molclr_gine_aggregate_fwd[_rowmax | _bf16] on its y, without
+ * the write of y and its re-read.  Segments as the BatchNorm's: seg_rows
+ * (host, summing to N) or, when not NULL, seg_rows_dev (device; N is then the
+ * row capacity and rows past the segments' sum are padding whose source reads
+ * as zero, the y the apply writes there).
+ * PRECONDITION: every in-edge of a row comes from a row of the same segment
+ * (true of a batched graph: edges stay inside one molecule); a row's sources
+ * take the coefficients of the row's own segment.
+ * rowparts (may be NULL) / slot (NULL without rowparts) as
+ * molclr_gine_aggregate_fwd_rowmax. */
+int molclr_gine_aggregate_bn_fwd(const float* z, const float* coeffs, int relu, int nseg,
+                                 const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                 const int32_t* rowptr, const int32_t* col, const uint8_t* ecode,
+                                 const uint32_t* nbr, const float* Ec, float* out, int64_t N,
+                                 int64_t D, float* rowparts, float* slot, molclr_stream_t stream);
 /* Backward: dx[j] = Σ_{k in out(j), edge order} g[dst_k] + g[j];
  * dE1[t] = Σ_i ecount[i][t] g[i], dE2[d] = Σ_i ecount[i][5+d] g[i].
  * dx may be NULL (first layer input needs no grad); dE1/dE2 may be NULL. */
@@ -611,6 +633,27 @@ int molclr_batchnorm_seg_fwd_dev(const void* z, const float* gamma, const float*
                                  int64_t rows_cap, int64_t dim, int dtype, double momentum,
                                  double eps, int training, int relu, void* workspace,
                                  size_t workspace_bytes, molclr_stream_t stream);
+/* molclr_batchnorm_seg_fwd / _fwd_dev without the apply: the same partition
+ * plan and kernels, the same save_mean / save_invstd, running statistics and
+ * num_batches_tracked, and the apply coefficients left at coeffs (scale
+ * [nseg,D], then shift [nseg,D]: y = fma(z, scale, shift)) for a consumer
+ * that applies them itself (molclr_gine_aggregate_bn_fwd).  No y is written.
+ * Workspace as the forward's. */
+int molclr_batchnorm_seg_coeffs(const void* z, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var,
+                                int64_t* num_batches_tracked, float* save_mean,
+                                float* save_invstd, float* coeffs, int nseg,
+                                const int64_t* seg_rows, int64_t dim, int dtype, double momentum,
+                                double eps, int training, void* workspace, size_t workspace_bytes,
+                                molclr_stream_t stream);
+int molclr_batchnorm_seg_coeffs_dev(const void* z, const float* gamma, const float* beta,
+                                    float* running_mean, float* running_var,
+                                    int64_t* num_batches_tracked, float* save_mean,
+                                    float* save_invstd, float* coeffs, int nseg,
+                                    const int64_t* seg_rows_dev, int64_t rows_cap, int64_t dim,
+                                    int dtype, double momentum, double eps, int training,
+                                    void* workspace, size_t workspace_bytes,
+                                    molclr_stream_t stream);
 int molclr_batchnorm_seg_bwd_dev(const void* dy, const void* z, const float* gamma,
                                  const float* beta, const float* save_mean,
                                  const float* save_invstd, void* dz, float* dgamma, float* dbeta,
@@ -942,6 +985,14 @@ int molclr_gine_aggregate_fwd_bf16(const uint16_t* x, const int32_t* rowptr, con
                                    const uint8_t* ecode, const uint32_t* nbr, const float* Ec,
                                    uint16_t* out, int64_t num_nodes, int64_t dim,
                                    molclr_stream_t stream);
+/* molclr_gine_aggregate_bn_fwd over bf16 storage: z, out bf16; every source
+ * element is the apply's y rounded to bf16 (as stored) and widened again. */
+int molclr_gine_aggregate_bn_fwd_bf16(const uint16_t* z, const float* coeffs, int relu, int nseg,
+                                      const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                      const int32_t* rowptr, const int32_t* col,
+                                      const uint8_t* ecode, const uint32_t* nbr, const float* Ec,
+                                      uint16_t* out, int64_t N, int64_t D,
+                                      molclr_stream_t stream);
 /* workspace: molclr_gine_aggregate_bwd_workspace_bytes */
 int molclr_gine_aggregate_bwd_bf16(const uint16_t* g, const int32_t* rowptr_t,
                                    const int32_t* col_t, const uint32_t* nbr_t,

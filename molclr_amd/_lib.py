@@ -48,6 +48,15 @@ SIGNATURES = {
     "molclr_rowmax_bytes": (c_size_t, [_I64, _I64]),
     "molclr_gine_aggregate_fwd_rowmax": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P,
                                                  _P]),
+    "molclr_gine_aggregate_bn_fwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _I64, _I64, _P, _P, _P]),
+    "molclr_gine_aggregate_bn_fwd_bf16": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
+                                                  _P, _I64, _I64, _P]),
+    "molclr_batchnorm_seg_coeffs": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _I64,
+                                            c_int, c_double, c_double, c_int, _P, c_size_t, _P]),
+    "molclr_batchnorm_seg_coeffs_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _I64,
+                                                _I64, c_int, c_double, c_double, c_int, _P,
+                                                c_size_t, _P]),
     "molclr_gine_aggregate_bwd_workspace_bytes": (c_size_t, [_I64, _I64]),
     "molclr_gine_aggregate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int, _P,
                                           c_size_t, _P]),

@@ -332,19 +332,78 @@ __device__ __forceinline__ float4 gine_msg(const float4* __restrict__ x, const f
   return f4add(x[(int64_t)nbr_node(w) * d4 + c], Ec[nbr_ecomb(w) * d4 + c]);
 }
 
+// Where the gather's source rows come from.  Plain: the stored rows x.
+// BatchNorm source (molclr_gine_aggregate_bn_fwd): x holds the BatchNorm INPUT
+// z and every element read, the self row's and the gathered rows', is
+// y = bn_apply1(z, scale, shift) (then ReLU) computed on the way in -- the
+// arithmetic of k_bn_apply, for bf16 storage rounded to bf16 as its store
+// rounds y and widened again, so the sums are those over a stored y, which is
+// neither written nor read back.  A lane takes the coefficients of its own
+// column for its DESTINATION row's segment: in a batched graph every in-edge
+// comes from the same graph, hence the same segment.  A padding row of a
+// device-sized plan reads zero, the y the apply writes there.
+struct NoSrcArgs {};
+struct BnSrcArgs {
+  const float4* scale;  // [nseg][D / 4]
+  const float4* shift;
+  int relu;
+  Segs sg;
+};
+
+template <typename St>
+__device__ __forceinline__ float4 bn_src_unit(float4 v, float4 sc, float4 sh, bool relu) {
+  float4 o = make_float4(bn_apply1(v.x, sc.x, sh.x), bn_apply1(v.y, sc.y, sh.y),
+                         bn_apply1(v.z, sc.z, sh.z), bn_apply1(v.w, sc.w, sh.w));
+  if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+  if constexpr (St::kBytes == 2) {  // as StBF16::st stores y and ::ld reads it
+    const uint32_t lo = f32x2_to_bf16x2(o.x, o.y), hi = f32x2_to_bf16x2(o.z, o.w);
+    o = make_float4(bf16_to_f32(lo & 0xFFFFu), bf16_to_f32(lo >> 16), bf16_to_f32(hi & 0xFFFFu),
+                    bf16_to_f32(hi >> 16));
+  }
+  return o;
+}
+
+// the source of destination row i, float4 column c: X(x, unit) is one column unit
+template <typename St, typename SA>
+struct AggSrc {
+  __device__ __forceinline__ AggSrc(const SA&, int64_t, int, int) {}
+  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x,
+                                               int64_t unit) const {
+    return St::ld(x, unit);
+  }
+};
+template <typename St>
+struct AggSrc<St, BnSrcArgs> {
+  float4 sc, sh;
+  bool relu, pad;
+  __device__ __forceinline__ AggSrc(const BnSrcArgs& a, int64_t i, int c, int d4) {
+    const int s = seg_of_row(a.sg, i);
+    pad = s < 0;
+    relu = a.relu != 0;
+    sc = pad ? f4zero() : a.scale[s * d4 + c];
+    sh = pad ? f4zero() : a.shift[s * d4 + c];
+  }
+  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x,
+                                               int64_t unit) const {
+    if (pad) return f4zero();
+    return bn_src_unit<St>(St::ld(x, unit), sc, sh, relu);
+  }
+};
+
 // Row i's neighbour entry is one 16-byte load shared by the row's D/4 lanes;
 // for degree <= 4 every gather is issued before the ordered adds, so the row
 // costs two dependent memory latencies (slots, then features).  Rows of
 // higher degree walk the CSR.  Order of the adds: in-edges in edge order,
 // self loop last — the reference's, so the sums are bit-identical.  One
 // float4 of the aggregation, stored and returned.
-template <typename St, bool NT = false>
+template <typename St, bool NT = false, typename SA = NoSrcArgs>
 __device__ __forceinline__ float4 gine_agg_elem(
     const typename St::T* __restrict__ x, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const uint8_t* __restrict__ ecode,
     const uint4* __restrict__ nbr, const float4* __restrict__ Ec, typename St::T* __restrict__ out,
-    int64_t t, int64_t i, int c, int d4) {
-  auto X = [&](int64_t idx) { return St::ld(x, idx); };
+    int64_t t, int64_t i, int c, int d4, const SA& sa) {
+  const AggSrc<St, SA> src(sa, i, c, d4);
+  auto X = [&](int64_t idx) { return src(x, idx); };
   auto msg = [&](uint32_t w) {
     return f4add(X((int64_t)nbr_node(w) * d4 + c), Ec[nbr_ecomb(w) * d4 + c]);
   };
@@ -379,12 +438,13 @@ __device__ __forceinline__ float4 gine_agg_elem(
 // ROWMAX: also the output's row maxima as row parts (row_max_parts) and, when
 // `slot` is given, its max -- the row scales of the h3 product that consumes it.
 // NT: non-temporal output stores (fp32; MOLCLR_AGG_NT=1, an A/B switch).
-template <typename St, bool ROWMAX, bool NT = false>
+// SA = BnSrcArgs: x is a BatchNorm input, applied on the way in (AggSrc).
+template <typename St, bool ROWMAX, bool NT = false, typename SA = NoSrcArgs>
 __global__ __launch_bounds__(kT) void k_gine_agg_fwd(
     const typename St::T* __restrict__ x, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const uint8_t* __restrict__ ecode,
     const uint4* __restrict__ nbr, const float4* __restrict__ Ec, typename St::T* __restrict__ out,
-    int64_t N, int d4, float* __restrict__ rowparts, int nparts, float* __restrict__ slot) {
+    int64_t N, int d4, float* __restrict__ rowparts, int nparts, float* __restrict__ slot, SA sa) {
   int64_t t = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   // (row, float4 column) of this lane: 32-bit division when the grid allows
   int64_t i;
@@ -402,7 +462,7 @@ __global__ __launch_bounds__(kT) void k_gine_agg_fwd(
     float m = 0.f;
     int row = -1;
     if (t < N * d4) {
-      const float4 v = gine_agg_elem<St, NT>(x, rowptr, col, ecode, nbr, Ec, out, t, i, c, d4);
+      const float4 v = gine_agg_elem<St, NT>(x, rowptr, col, ecode, nbr, Ec, out, t, i, c, d4, sa);
       m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
       row = (int)i;
     }
@@ -417,7 +477,7 @@ __global__ __launch_bounds__(kT) void k_gine_agg_fwd(
     return;
   }
   if (t >= N * d4) return;
-  gine_agg_elem<St, NT>(x, rowptr, col, ecode, nbr, Ec, out, t, i, c, d4);
+  gine_agg_elem<St, NT>(x, rowptr, col, ecode, nbr, Ec, out, t, i, c, d4, sa);
 }
 
 // dx[j] = Σ_{out-edges of j in edge order} g[dst] + g[j]  (neighbour slots of the CSC).
@@ -663,20 +723,51 @@ __device__ __forceinline__ F8 ec8(const float4* __restrict__ Ec, int comb, int d
   return {e[0], e[1]};
 }
 
+// the source of destination row i, 8-column unit c (AggSrc for 16-byte units)
+template <typename SA>
+struct AggSrc8 {
+  __device__ __forceinline__ AggSrc8(const SA&, int64_t, int, int) {}
+  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit) const {
+    return ld8(x, unit);
+  }
+};
+template <>
+struct AggSrc8<BnSrcArgs> {
+  float4 sc[2], sh[2];
+  bool relu, pad;
+  __device__ __forceinline__ AggSrc8(const BnSrcArgs& a, int64_t i, int c, int d8) {
+    const int s = seg_of_row(a.sg, i);
+    pad = s < 0;
+    relu = a.relu != 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      sc[j] = pad ? f4zero() : a.scale[(s * d8 + c) * 2 + j];
+      sh[j] = pad ? f4zero() : a.shift[(s * d8 + c) * 2 + j];
+    }
+  }
+  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit) const {
+    if (pad) return {f4zero(), f4zero()};
+    const F8 v = ld8(x, unit);
+    return {bn_src_unit<StBF16>(v.a, sc[0], sh[0], relu), bn_src_unit<StBF16>(v.b, sc[1], sh[1], relu)};
+  }
+};
+
+template <typename SA = NoSrcArgs>
 __global__ __launch_bounds__(kT) void k_gine_agg_fwd_b8(
     const uint16_t* __restrict__ x, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const uint8_t* __restrict__ ecode,
     const uint4* __restrict__ nbr, const float4* __restrict__ Ec, uint16_t* __restrict__ out,
-    int64_t N, int d8) {
+    int64_t N, int d8, SA sa) {
   int64_t t = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   if (t >= N * d8) return;
   const int64_t i = t / d8;
   const int c = (int)(t - i * d8);
+  const AggSrc8<SA> src(sa, i, c, d8);
   auto msg = [&](uint32_t w) {
-    return f8add(ld8(x, (int64_t)nbr_node(w) * d8 + c), ec8(Ec, nbr_ecomb(w), d8, c));
+    return f8add(src(x, (int64_t)nbr_node(w) * d8 + c), ec8(Ec, nbr_ecomb(w), d8, c));
   };
   const uint4 s = nbr[i];
-  const F8 self = ld8(x, t);
+  const F8 self = src(x, t);
   const F8 es = ec8(Ec, MOLCLR_SELF_LOOP_ECOMB, d8, c);
   const uint32_t deg = nbr_degree(s.x);
   F8 acc = {f4zero(), f4zero()};
@@ -691,7 +782,7 @@ __global__ __launch_bounds__(kT) void k_gine_agg_fwd_b8(
     if (deg > 3) acc = f8add(acc, m3);
   } else {
     for (int32_t k = rowptr[i], e = rowptr[i + 1]; k < e; ++k)
-      acc = f8add(acc, f8add(ld8(x, (int64_t)col[k] * d8 + c), ec8(Ec, MOLCLR_ECOMB(ecode[k]), d8, c)));
+      acc = f8add(acc, f8add(src(x, (int64_t)col[k] * d8 + c), ec8(Ec, MOLCLR_ECOMB(ecode[k]), d8, c)));
   }
   st8(out, t, f8add(acc, f8add(self, es)));
 }
@@ -883,7 +974,7 @@ MOLCLR_API int molclr_gine_aggregate_fwd(const float* x, const int32_t* rowptr,
                                                       : k_gine_agg_fwd<StF32, false, false>,
                        dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
                        x, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d4,
-                       nullptr, 0, nullptr);
+                       nullptr, 0, nullptr, NoSrcArgs{});
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
@@ -915,7 +1006,7 @@ MOLCLR_API int molclr_gine_aggregate_fwd_rowmax(const float* x, const int32_t* r
                                                       : k_gine_agg_fwd<StF32, true, false>,
                        dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
                        x, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d4,
-                       rowparts, (int)molclr_rowmax_layout(D), slot);
+                       rowparts, (int)molclr_rowmax_layout(D), slot, NoSrcArgs{});
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
@@ -1055,15 +1146,107 @@ MOLCLR_API int molclr_gine_aggregate_fwd_bf16(const uint16_t* x, const int32_t* 
   MOLCLR_REQUIRE(x && rowptr && nbr && Ec && out, "gine_aggregate_fwd_bf16: null pointer");
   if (D % 8 == 0) {
     const int d8 = (int)(D / 8);
-    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd_b8, dim3(molclr::ceil_div(N * d8, kT)),
-                         dim3(kT), 0, molclr::as_stream(stream), x, rowptr, col, ecode,
-                         (const uint4*)nbr, (const float4*)Ec, out, N, d8);
+    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd_b8<NoSrcArgs>,
+                         dim3(molclr::ceil_div(N * d8, kT)), dim3(kT), 0, molclr::as_stream(stream),
+                         x, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d8,
+                         NoSrcArgs{});
   } else {
     const int d4 = (int)(D / 4);
     molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd<StBF16, false>,
                          dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
                          x, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d4,
-                         nullptr, 0, nullptr);
+                         nullptr, 0, nullptr, NoSrcArgs{});
+  }
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+// BatchNorm source: the segments of the rows, host- or device-sized
+static int agg_bn_args(const char* who, const float* coeffs, int relu, int nseg,
+                       const int64_t* seg_rows, const int64_t* seg_rows_dev, int64_t N, int64_t D,
+                       BnSrcArgs& a) {
+  MOLCLR_REQUIRE(coeffs && ((uintptr_t)coeffs & 15) == 0, "%s: coeffs null or not 16-byte aligned", who);
+  MOLCLR_REQUIRE(nseg >= 1 && nseg <= MOLCLR_MAX_SEGMENTS && (seg_rows || seg_rows_dev),
+                 "%s: %d segments (1..%d)", who, nseg, MOLCLR_MAX_SEGMENTS);
+  a.scale = reinterpret_cast<const float4*>(coeffs);
+  a.shift = reinterpret_cast<const float4*>(coeffs + (size_t)nseg * D);
+  a.relu = relu;
+  a.sg.n = nseg;
+  a.sg.band = 0;  // no partition plan here
+  a.sg.drows = seg_rows_dev;
+  int64_t tot = 0;
+  for (int s = 0; s < MOLCLR_MAX_SEGMENTS; ++s) {
+    a.sg.rows[s] = (!seg_rows_dev && s < nseg) ? seg_rows[s] : 0;
+    MOLCLR_REQUIRE(a.sg.rows[s] >= 0, "%s: negative segment rows", who);
+    tot += a.sg.rows[s];
+  }
+  MOLCLR_REQUIRE(seg_rows_dev || tot == N, "%s: segments sum to %lld rows, N = %lld", who,
+                 (long long)tot, (long long)N);
+  return MOLCLR_OK;
+}
+
+MOLCLR_API int molclr_gine_aggregate_bn_fwd(const float* z, const float* coeffs, int relu, int nseg,
+                                            const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                            const int32_t* rowptr, const int32_t* col,
+                                            const uint8_t* ecode, const uint32_t* nbr,
+                                            const float* Ec, float* out, int64_t N, int64_t D,
+                                            float* rowparts, float* slot, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bn_fwd: dim %lld must be a multiple of 4",
+                 (long long)D);
+  MOLCLR_REQUIRE(N < (1ll << 31), "gine_aggregate_bn_fwd: too many rows");
+  MOLCLR_REQUIRE(rowparts || !slot, "gine_aggregate_bn_fwd: a slot needs rowparts");
+  if (N == 0) return MOLCLR_OK;
+  MOLCLR_REQUIRE(z && rowptr && nbr && Ec && out, "gine_aggregate_bn_fwd: null pointer");
+  BnSrcArgs a;
+  MOLCLR_TRY_RC(agg_bn_args("gine_aggregate_bn_fwd", coeffs, relu, nseg, seg_rows, seg_rows_dev, N,
+                            D, a));
+  const int d4 = (int)(D / 4);
+  const dim3 grid(molclr::ceil_div(N * d4, kT));
+  hipStream_t s = molclr::as_stream(stream);
+  const uint4* nb = (const uint4*)nbr;
+  const float4* ec = (const float4*)Ec;
+  if (rowparts) {
+    const int np = (int)molclr_rowmax_layout(D);
+    molclr::launch_timed(molclr::kTimeGineAgg,
+                         agg_nt() ? k_gine_agg_fwd<StF32, true, true, BnSrcArgs>
+                                  : k_gine_agg_fwd<StF32, true, false, BnSrcArgs>,
+                         grid, dim3(kT), 0, s, z, rowptr, col, ecode, nb, ec, out, N, d4, rowparts,
+                         np, slot, a);
+  } else {
+    molclr::launch_timed(molclr::kTimeGineAgg,
+                         agg_nt() ? k_gine_agg_fwd<StF32, false, true, BnSrcArgs>
+                                  : k_gine_agg_fwd<StF32, false, false, BnSrcArgs>,
+                         grid, dim3(kT), 0, s, z, rowptr, col, ecode, nb, ec, out, N, d4,
+                         (float*)nullptr, 0, (float*)nullptr, a);
+  }
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+MOLCLR_API int molclr_gine_aggregate_bn_fwd_bf16(const uint16_t* z, const float* coeffs, int relu,
+                                                 int nseg, const int64_t* seg_rows,
+                                                 const int64_t* seg_rows_dev,
+                                                 const int32_t* rowptr, const int32_t* col,
+                                                 const uint8_t* ecode, const uint32_t* nbr,
+                                                 const float* Ec, uint16_t* out, int64_t N,
+                                                 int64_t D, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bn_fwd_bf16: dim must be a multiple of 4");
+  if (N == 0) return MOLCLR_OK;
+  MOLCLR_REQUIRE(z && rowptr && nbr && Ec && out, "gine_aggregate_bn_fwd_bf16: null pointer");
+  BnSrcArgs a;
+  MOLCLR_TRY_RC(agg_bn_args("gine_aggregate_bn_fwd_bf16", coeffs, relu, nseg, seg_rows,
+                            seg_rows_dev, N, D, a));
+  if (D % 8 == 0) {
+    const int d8 = (int)(D / 8);
+    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd_b8<BnSrcArgs>,
+                         dim3(molclr::ceil_div(N * d8, kT)), dim3(kT), 0, molclr::as_stream(stream),
+                         z, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d8, a);
+  } else {
+    const int d4 = (int)(D / 4);
+    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd<StBF16, false, false, BnSrcArgs>,
+                         dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
+                         z, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d4,
+                         (float*)nullptr, 0, (float*)nullptr, a);
   }
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;

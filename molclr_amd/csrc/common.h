@@ -312,6 +312,37 @@ struct StBF16 {
   }
 };
 
+// ---------------------------------------------------------------------------
+// Row segments (norm.hip's segmented BatchNorm; aggregate.hip's BatchNorm
+// source): the rows are `n` consecutive segments, host- or device-sized.
+// ---------------------------------------------------------------------------
+struct Segs {
+  int n;     // segments
+  int band;  // the partition plan's row unit (make_band(D).band)
+  int64_t rows[MOLCLR_MAX_SEGMENTS];  // host-sized: rows of every segment
+  // device-sized (a captured step over padded buffers): the rows of every
+  // segment live on the device and rows[] is unused; rows past the last
+  // segment are padding -- zero output, zero gradient, no statistics
+  const int64_t* drows;
+};
+
+__device__ __forceinline__ int64_t seg_n(const Segs& sg, int s) {
+  return sg.drows ? sg.drows[s] : sg.rows[s];
+}
+// the segment of row i; -1 for a padding row of a device-sized plan
+__device__ __forceinline__ int seg_of_row(const Segs& sg, int64_t i) {
+  int64_t r = 0;
+  for (int s = 0; s < sg.n; ++s) {
+    r += seg_n(sg, s);
+    if (i < r) return s;
+  }
+  return -1;
+}
+
+// BatchNorm apply of one element (k_bn_apply, and the aggregation that applies
+// it to its source on the fly): one fused multiply-add, ReLU by the caller
+__device__ __forceinline__ float bn_apply1(float z, float sc, float sh) { return __fmaf_rn(z, sc, sh); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

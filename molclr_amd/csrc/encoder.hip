@@ -8,20 +8,37 @@
 // only the host cost goes.
 //
 // Arena (saved for the backward), per layer l: agg_l [N,D], a1_l [N,2D],
-// z_l [N,D], h_l [N,D] (BatchNorm output, the next layer's input; the last
-// layer writes h_out instead), mean_l / invstd_l [D]; then h0 [N,D] (atom
-// embedding) and the combined edge tables Ec [L,15,D].
+// z_l [N,D], mean_l / invstd_l [D] and the BatchNorm apply coefficients
+// coef_l [2][segments][D]; then h0 [N,D] (atom embedding) and the combined
+// edge tables Ec [L,15,D].  The BatchNorm output h_l of every layer but the
+// last is never stored: layer l + 1's aggregation applies coef_l to z_l as it
+// gathers (molclr_gine_aggregate_bn_fwd; the backward reads z, never h).  The
+// last layer's apply writes h_out.  MOLCLR_AGG_BN=0 (an A/B switch) keeps the
+// stored h_l [N,D] and the plain gather.
 // Workspace: backward scratch dh, dz, dagg [N,D] + dz1 [N,2D], then the
 // largest workspace any called entry point asks for.
 #include "common.h"
 
+#include <stdlib.h>
+
 namespace {
+
+// the next layer's aggregation applies the BatchNorm (default) or reads a
+// stored h_l (MOLCLR_AGG_BN=0)
+bool agg_bn() {
+  static const bool on = [] {
+    const char* e = getenv("MOLCLR_AGG_BN");
+    return !(e != nullptr && e[0] == '0');
+  }();
+  return on;
+}
 
 // byte offsets; node-feature buffers in the encoder's storage type (fp32 or
 // bf16), statistics and edge tables fp32; every buffer 256-byte aligned
 struct ArenaLayout {
   size_t agg[MOLCLR_MAX_LAYERS], a1[MOLCLR_MAX_LAYERS], z[MOLCLR_MAX_LAYERS],
-      h[MOLCLR_MAX_LAYERS], mean[MOLCLR_MAX_LAYERS], invstd[MOLCLR_MAX_LAYERS];
+      h[MOLCLR_MAX_LAYERS], mean[MOLCLR_MAX_LAYERS], invstd[MOLCLR_MAX_LAYERS],
+      coef[MOLCLR_MAX_LAYERS];
   size_t bits[MOLCLR_MAX_LAYERS];  // h3: ReLU mask of a1_l as bits [ceil(2D / 32)][N]
   size_t h0, ec, smax, bmax, total;
   ArenaLayout(int L, int64_t N, int64_t D, size_t es) {
@@ -35,9 +52,10 @@ struct ArenaLayout {
       agg[l] = off(N * D * es);
       a1[l] = off(N * 2 * D * es);
       z[l] = off(N * D * es);
-      h[l] = off(N * D * es);
+      h[l] = agg_bn() ? 0 : off(N * D * es);  // stored only on the MOLCLR_AGG_BN=0 path
       mean[l] = off(MOLCLR_MAX_SEGMENTS * D * sizeof(float));  // [segment][D]
       invstd[l] = off(MOLCLR_MAX_SEGMENTS * D * sizeof(float));
+      coef[l] = off(2 * MOLCLR_MAX_SEGMENTS * D * sizeof(float));  // scale, shift [segment][D]
       bits[l] = off((size_t)N * ((2 * D + 31) / 32) * sizeof(uint32_t));
     }
     h0 = off(N * D * es);
@@ -133,6 +151,19 @@ int seg_bn_fwd(const SegRows& sg, const void* z, const float* gamma, const float
                                   sg.rows, D, dtype, momentum, eps, training, relu, ws, ws_bytes,
                                   stream);
 }
+// its statistics and apply coefficients only (coef: scale, shift [sg.n][D])
+int seg_bn_coeffs(const SegRows& sg, const void* z, const float* gamma, const float* beta,
+                  float* rmean, float* rvar, int64_t* nbt, float* mean, float* invstd, float* coef,
+                  int64_t D, int dtype, double momentum, double eps, int training, void* ws,
+                  size_t ws_bytes, molclr_stream_t stream) {
+  if (sg.dev)
+    return molclr_batchnorm_seg_coeffs_dev(z, gamma, beta, rmean, rvar, nbt, mean, invstd, coef,
+                                           sg.n, sg.dev, sg.cap, D, dtype, momentum, eps, training,
+                                           ws, ws_bytes, stream);
+  return molclr_batchnorm_seg_coeffs(z, gamma, beta, rmean, rvar, nbt, mean, invstd, coef, sg.n,
+                                     sg.rows, D, dtype, momentum, eps, training, ws, ws_bytes,
+                                     stream);
+}
 // rowmax != NULL (fp32): also dz's row maxima and max slot (the h3 scales)
 int seg_bn_bwd(const SegRows& sg, const void* dy, const void* z, const float* gamma,
                const float* beta, const float* mean, const float* invstd, void* dz, float* dgamma,
@@ -224,6 +255,8 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
   const bool h3f = h3 && (e->fp32_gemm & 2);  // h3 forward products (not the default)
   float* fmax = F(lay.smax);  // h3: [l][0] = max |agg_l|, [l][1] = max |a1_l|
 
+  // layer l > 0 gathers from z_{l-1} through coef_{l-1} (fused), else from h
+  const bool fused = agg_bn();
   void* h = A + lay.h0;
   if (bf)
     MOLCLR_TRY(molclr_atom_embed_fwd_bf16(x, e->x_embedding1, e->x_embedding2, (uint16_t*)h, N, D,
@@ -239,12 +272,21 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
                                               h3 ? fmax : nullptr, nz, stream));
   for (int l = 0; l < L; ++l) {
     const bool last = l == L - 1;
-    void* y = last ? h_out : A + lay.h[l];
+    const bool bn_src = fused && l > 0;   // this layer's source: z_{l-1} with coef_{l-1}
+    const bool bn_next = fused && !last;  // this layer's BatchNorm: coefficients only
+    void* y = last ? h_out : bn_next ? nullptr : A + lay.h[l];
     const float* Ecl = Ec + (size_t)l * MOLCLR_NUM_ECOMB * D;
+    const void* zp = bn_src ? A + lay.z[l - 1] : nullptr;
+    const float* cp = bn_src ? F(lay.coef[l - 1]) : nullptr;
     if (bf) {
       uint16_t *agg = H(lay.agg[l]), *a1 = H(lay.a1[l]), *z = H(lay.z[l]);
-      MOLCLR_TRY(molclr_gine_aggregate_fwd_bf16((const uint16_t*)h, g->rowptr, g->col, g->ecode,
-                                                g->nbr, Ecl, agg, N, D, stream));
+      if (bn_src)
+        MOLCLR_TRY(molclr_gine_aggregate_bn_fwd_bf16((const uint16_t*)zp, cp, 1, seg.n, seg.rows,
+                                                     seg.dev, g->rowptr, g->col, g->ecode, g->nbr,
+                                                     Ecl, agg, N, D, stream));
+      else
+        MOLCLR_TRY(molclr_gine_aggregate_fwd_bf16((const uint16_t*)h, g->rowptr, g->col, g->ecode,
+                                                  g->nbr, Ecl, agg, N, D, stream));
       // GINEConv.update in bf16: one MFMA per product, fp32 accumulation; the
       // first product also writes a1's ReLU mask as bits for the backward
       if (D % 64 == 0)
@@ -256,14 +298,26 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
                                     MOLCLR_EPI_BIAS_RELU, e->mlp0_bias[l], nullptr, 0, stream));
       MOLCLR_TRY(molclr_gemm_bf16(a1, e->mlp2_planes[l], z, N, D, 2 * D, 2 * D, D,
                                   MOLCLR_EPI_BIAS, e->mlp2_bias[l], nullptr, 0, stream));
-      MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
-                            e->bn_running_var[l], e->bn_num_batches_tracked[l], y, F(lay.mean[l]),
-                            F(lay.invstd[l]), D, MOLCLR_DTYPE_BF16, e->momentum, e->eps,
-                            e->training, last ? 0 : 1, kws, kws_bytes, stream));
+      if (bn_next)
+        MOLCLR_TRY(seg_bn_coeffs(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
+                                 e->bn_running_var[l], e->bn_num_batches_tracked[l],
+                                 F(lay.mean[l]), F(lay.invstd[l]), F(lay.coef[l]), D,
+                                 MOLCLR_DTYPE_BF16, e->momentum, e->eps, e->training, kws,
+                                 kws_bytes, stream));
+      else
+        MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
+                              e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
+                              F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_BF16, e->momentum,
+                              e->eps, e->training, last ? 0 : 1, kws, kws_bytes, stream));
     } else {
       float *agg = F(lay.agg[l]), *a1 = F(lay.a1[l]), *z = F(lay.z[l]);
       float* sl = fmax + 2 * l * kMaxSlotFloats;
-      if (h3f)  // agg's row maxima from the aggregation itself, max |agg| from lin1
+      // h3 forward: agg's row maxima from the aggregation itself, max |agg| from lin1
+      if (bn_src)
+        MOLCLR_TRY(molclr_gine_aggregate_bn_fwd((const float*)zp, cp, 1, seg.n, seg.rows, seg.dev,
+                                                g->rowptr, g->col, g->ecode, g->nbr, Ecl, agg, N,
+                                                D, h3f ? ragg : nullptr, nullptr, stream));
+      else if (h3f)
         MOLCLR_TRY(molclr_gine_aggregate_fwd_rowmax((const float*)h, g->rowptr, g->col, g->ecode,
                                                     g->nbr, Ecl, agg, N, D, ragg, nullptr,
                                                     stream));
@@ -303,10 +357,17 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
                                            MOLCLR_EPI_BIAS, e->mlp2_bias[l], nullptr, 0, kws,
                                            kws_bytes, stream));
       }
-      MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
-                            e->bn_running_var[l], e->bn_num_batches_tracked[l], y, F(lay.mean[l]),
-                            F(lay.invstd[l]), D, MOLCLR_DTYPE_F32, e->momentum, e->eps,
-                            e->training, last ? 0 : 1, kws, kws_bytes, stream));
+      if (bn_next)
+        MOLCLR_TRY(seg_bn_coeffs(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
+                                 e->bn_running_var[l], e->bn_num_batches_tracked[l],
+                                 F(lay.mean[l]), F(lay.invstd[l]), F(lay.coef[l]), D,
+                                 MOLCLR_DTYPE_F32, e->momentum, e->eps, e->training, kws, kws_bytes,
+                                 stream));
+      else
+        MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
+                              e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
+                              F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_F32, e->momentum,
+                              e->eps, e->training, last ? 0 : 1, kws, kws_bytes, stream));
     }
     h = y;
   }

@@ -122,22 +122,9 @@ __global__ __launch_bounds__(kRedCols* kRedLanes) void k_colsum_final(
 // segment, in segment order.  A segment is partitioned exactly as a
 // one-segment call over its rows would be, so every per-segment result is
 // bit-identical to that call.  Storage of z / y / dy / dz is fp32 or bf16
-// (StF32 / StBF16); the statistics are always fp32.
+// (StF32 / StBF16); the statistics are always fp32.  Segs / seg_of_row:
+// common.h (shared with the aggregation that applies the coefficients).
 // ---------------------------------------------------------------------------
-struct Segs {
-  int n;     // segments
-  int band;  // the partition plan's row unit (make_band(D).band)
-  int64_t rows[MOLCLR_MAX_SEGMENTS];  // host-sized: rows of every segment
-  // device-sized (a captured step over padded buffers): the rows of every
-  // segment live on the device and rows[] is unused; rows past the last
-  // segment are padding -- zero output, zero gradient, no statistics
-  const int64_t* drows;
-};
-
-__device__ __forceinline__ int64_t seg_n(const Segs& sg, int s) {
-  return sg.drows ? sg.drows[s] : sg.rows[s];
-}
-
 // Segment s's rows [row0, row1) and partitions [part0, part0 + P), each
 // partition rpp rows: exactly a one-segment call's plan over its rows.  s = -1
 // for a spare partition / padding row of a device-sized plan.
@@ -168,14 +155,6 @@ __device__ __forceinline__ SegAt seg_of_part(const Segs& sg, int64_t b) {
 // t / d4 in 32 bits when the whole index range fits (uniform branch)
 __device__ __forceinline__ int64_t row_of(int64_t t, int d4, int64_t total4) {
   return total4 <= 0x7FFFFFFF ? (int64_t)((uint32_t)t / (uint32_t)d4) : t / d4;
-}
-__device__ __forceinline__ int seg_of_row(const Segs& sg, int64_t i) {
-  int64_t r = 0;
-  for (int s = 0; s < sg.n; ++s) {
-    r += seg_n(sg, s);
-    if (i < r) return s;
-  }
-  return -1;
 }
 
 struct Welford4 {
@@ -374,8 +353,6 @@ __global__ void k_bn_eval_coeffs(const float* __restrict__ gamma, const float* _
     shift[s * D + c] = sh;
   }
 }
-
-__device__ __forceinline__ float bn_apply1(float z, float sc, float sh) { return __fmaf_rn(z, sc, sh); }
 
 // U = 2 (bf16 storage): two column units per thread, one 16-byte access each
 // way (8-byte bf16 accesses ran at half the HBM rate of the fp32 form); the
@@ -901,13 +878,23 @@ size_t bn_ws_bytes(int64_t P, int64_t D, int nseg) {
   return w.used + 256;
 }
 
-template <typename St>
-int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running_mean,
-           float* running_var, int64_t* nbt, void* yv, float* save_mean, float* save_invstd,
-           int nseg, const int64_t* seg_rows, int64_t D, double momentum, double eps, int training,
-           int relu, void* workspace, size_t workspace_bytes, hipStream_t s,
-           const int64_t* drows = nullptr, int64_t cap = 0) {
+// The forward up to the apply: batch statistics (training) or the running
+// ones (eval), save_mean / save_invstd, the running-statistics update, and the
+// apply coefficients scale / shift [nseg][D] -- at `coeffs` (scale, then
+// shift) when given, else in the workspace.  `plan` returns the segment plan
+// and the coefficients for the apply.
+struct BnPlan {
   Segs sg;
+  int64_t rows;
+  const float *scale, *shift;
+};
+template <typename St>
+int bn_fwd_coeffs(const void* zv, const float* gamma, const float* beta, float* running_mean,
+                  float* running_var, int64_t* nbt, float* save_mean, float* save_invstd,
+                  float* coeffs, int nseg, const int64_t* seg_rows, int64_t D, double momentum,
+                  double eps, int training, void* workspace, size_t workspace_bytes, hipStream_t s,
+                  const int64_t* drows, int64_t cap, BnPlan& plan) {
+  Segs& sg = plan.sg;
   int64_t P = 0, rows = 0;
   if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
   MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "batchnorm_fwd: dim must be a multiple of 4");
@@ -918,7 +905,6 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
   MOLCLR_REQUIRE(save_mean && save_invstd && (rows == 0 || zv), "batchnorm_fwd: null pointer");
   MOLCLR_REQUIRE_WS(workspace_bytes, bn_ws_bytes(P, D, nseg));
   const auto* z = static_cast<const typename St::T*>(zv);
-  auto* y = static_cast<typename St::T*>(yv);
   const molclr::Band b = molclr::make_band(D);
   molclr::Workspace w(workspace, workspace_bytes);
   float* pmean = w.take<float>(P * D);
@@ -926,6 +912,10 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
   float* pn = w.take<float>(P);
   float* scale = w.take<float>(nseg * D);
   float* shift = w.take<float>(nseg * D);
+  if (coeffs) {
+    scale = coeffs;
+    shift = coeffs + (size_t)nseg * D;
+  }
   if (training) {
     const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
     hipLaunchKernelGGL(k_bn_stats_partial<St>, dim3((unsigned)P), dim3(b.threads), lds, s, z, b.d4,
@@ -939,7 +929,29 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
                        beta, running_mean, running_var, D, nseg, (float)eps, save_mean,
                        save_invstd, scale, shift);
   }
-  const int64_t total4 = rows * (D / 4);
+  plan.rows = rows;
+  plan.scale = scale;
+  plan.shift = shift;
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+template <typename St>
+int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running_mean,
+           float* running_var, int64_t* nbt, void* yv, float* save_mean, float* save_invstd,
+           int nseg, const int64_t* seg_rows, int64_t D, double momentum, double eps, int training,
+           int relu, void* workspace, size_t workspace_bytes, hipStream_t s,
+           const int64_t* drows = nullptr, int64_t cap = 0) {
+  BnPlan plan;
+  if (int rc = bn_fwd_coeffs<St>(zv, gamma, beta, running_mean, running_var, nbt, save_mean,
+                                 save_invstd, nullptr, nseg, seg_rows, D, momentum, eps, training,
+                                 workspace, workspace_bytes, s, drows, cap, plan))
+    return rc;
+  const auto* z = static_cast<const typename St::T*>(zv);
+  auto* y = static_cast<typename St::T*>(yv);
+  const Segs& sg = plan.sg;
+  const float *scale = plan.scale, *shift = plan.shift;
+  const int64_t total4 = plan.rows * (D / 4);
   if (total4 > 0 && y) {  // y == NULL: statistics only (the consumer applies them)
     if (St::kBytes == 2 && D % 8 == 0)
       hipLaunchKernelGGL((k_bn_apply<St, 2>), dim3(molclr::ceil_div(total4 / 2, kT)), dim3(kT), 0,
@@ -1104,6 +1116,53 @@ MOLCLR_API int molclr_batchnorm_seg_fwd_dev(const void* z, const float* gamma, c
   return bn_fwd<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
                         save_mean, save_invstd, nseg, nullptr, D, momentum, eps, training, relu,
                         workspace, workspace_bytes, s, seg_rows_dev, rows_cap);
+}
+
+// The forward without the apply (molclr_gine_aggregate_bn_fwd applies the
+// coefficients to its source): same plan, kernels and statistics as
+// molclr_batchnorm_seg_fwd / _fwd_dev, scale / shift [nseg][D] left at coeffs.
+MOLCLR_API int molclr_batchnorm_seg_coeffs(const void* z, const float* gamma, const float* beta,
+                                           float* running_mean, float* running_var,
+                                           int64_t* num_batches_tracked, float* save_mean,
+                                           float* save_invstd, float* coeffs, int nseg,
+                                           const int64_t* seg_rows, int64_t D, int dtype,
+                                           double momentum, double eps, int training,
+                                           void* workspace, size_t workspace_bytes,
+                                           molclr_stream_t stream) {
+  MOLCLR_REQUIRE(coeffs, "batchnorm_seg_coeffs: null coeffs");
+  hipStream_t s = molclr::as_stream(stream);
+  BnPlan plan;
+  if (dtype == MOLCLR_DTYPE_F32)
+    return bn_fwd_coeffs<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                                save_mean, save_invstd, coeffs, nseg, seg_rows, D, momentum, eps,
+                                training, workspace, workspace_bytes, s, nullptr, 0, plan);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_coeffs: dtype %d", dtype);
+  return bn_fwd_coeffs<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                               save_mean, save_invstd, coeffs, nseg, seg_rows, D, momentum, eps,
+                               training, workspace, workspace_bytes, s, nullptr, 0, plan);
+}
+
+MOLCLR_API int molclr_batchnorm_seg_coeffs_dev(const void* z, const float* gamma, const float* beta,
+                                               float* running_mean, float* running_var,
+                                               int64_t* num_batches_tracked, float* save_mean,
+                                               float* save_invstd, float* coeffs, int nseg,
+                                               const int64_t* seg_rows_dev, int64_t rows_cap,
+                                               int64_t D, int dtype, double momentum, double eps,
+                                               int training, void* workspace,
+                                               size_t workspace_bytes, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(coeffs && seg_rows_dev, "batchnorm_seg_coeffs_dev: null coeffs / seg_rows_dev");
+  hipStream_t s = molclr::as_stream(stream);
+  BnPlan plan;
+  if (dtype == MOLCLR_DTYPE_F32)
+    return bn_fwd_coeffs<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                                save_mean, save_invstd, coeffs, nseg, nullptr, D, momentum, eps,
+                                training, workspace, workspace_bytes, s, seg_rows_dev, rows_cap,
+                                plan);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_coeffs_dev: dtype %d", dtype);
+  return bn_fwd_coeffs<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                               save_mean, save_invstd, coeffs, nseg, nullptr, D, momentum, eps,
+                               training, workspace, workspace_bytes, s, seg_rows_dev, rows_cap,
+                               plan);
 }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd_dev(const void* dy, const void* z, const float* gamma,
