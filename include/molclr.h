@@ -1056,6 +1056,86 @@ int molclr_linear_wgrad_bf16_impl(const uint16_t* dy, const uint16_t* x, float* 
                                   int64_t ld_x, int accumulate, void* workspace,
                                   size_t workspace_bytes, molclr_stream_t stream, int impl);
 
+/* ---- Supervised task head (fine-tuning) --------------------------------------
+ * The readout of the reference's fine-tuning models after the pooling
+ * (models/ginet_finetune.py:95-127,145-147, models/gcn_finetune.py:131-164)
+ * with finetune.py:71-77's criterion, as one chain:
+ *   a_0 = x [rows, dims[0]];  a_l = act_l(a_{l-1} W_l^T + b_l),  l = 1..L
+ * W_l [dims[l], dims[l-1]] row-major fp32 as nn.Linear stores it, L <=
+ * MOLCLR_TASK_HEAD_MAX_LAYERS, any rows >= 1 and any width in [1,
+ * MOLCLR_TASK_HEAD_MAX_DIM] (no multiple-of-4 rule; wider: MOLCLR_ERR_UNSUPPORTED,
+ * the row block's activations no longer fit the LDS -- molclr_amd.ops composes
+ * such chains from the GEMMs).  Every a_l is written to a[l-1] ([rows, dims[l]], dense):
+ * the backward reads them, and the models return a_1 (h) and a_L (pred).
+ * Softplus is nn.Softplus() (beta 1, threshold 20); its derivative is
+ * recomputed from the saved a_l as -expm1(-a_l).
+ * Loss on pred = a_L:
+ *   CROSS_ENTROPY  target int64 [rows], dims[L] <= MOLCLR_TASK_HEAD_MAX_CLASSES:
+ *       mean_rows(logsumexp(pred) - pred[y]), row max subtracted.  A label
+ *       outside [0, dims[L]) is never used as an index: it sets
+ *       MOLCLR_STATUS_LABEL_RANGE in *status (nullable) and its row's loss and
+ *       gradient are NaN.
+ *   MSE / L1       target float [rows, dims[L]], mean over all elements
+ *       (L1's gradient is sign(diff), 0 at diff == 0).
+ * The scalar goes to *loss_out.  The mean is a fixed-order sum (no floating
+ * point atomics anywhere): results are bit-identical from run to run.  `sync`
+ * is an int32 device word that is 0 on entry and 0 again when the forward
+ * has finished (the ticket of the workgroup that reduces the rows); calls that
+ * may overlap need their own word.
+ * Forward: one launch.  Backward: two launches -- the deltas of every layer
+ * down to dx (row-blocked; *gloss scales the loss term, dh / dpred are optional
+ * extra gradients into a_1 / a_L, gloss NULL = no loss term), then dW_l =
+ * delta_l^T a_{l-1} and db_l = sum_rows delta_l of all layers in one grid, each
+ * element summed over the rows in ascending order; accumulate[l] adds into
+ * dweight[l] / dbias[l] instead of overwriting.  A NULL dx, dweight[l] or
+ * dbias[l] is not computed.  Both directions take a workspace of
+ * molclr_task_head_workspace_bytes (0 for an invalid descriptor). */
+#define MOLCLR_TASK_HEAD_MAX_LAYERS 10
+#define MOLCLR_TASK_HEAD_MAX_CLASSES 16
+#define MOLCLR_TASK_HEAD_MAX_DIM 2044
+#define MOLCLR_STATUS_LABEL_RANGE 16 /* status bit: class label outside [0, C) */
+enum { MOLCLR_ACT_NONE = 0, MOLCLR_ACT_RELU = 1, MOLCLR_ACT_SOFTPLUS = 2 };
+enum {
+  MOLCLR_LOSS_NONE = 0,
+  MOLCLR_LOSS_CROSS_ENTROPY = 1,
+  MOLCLR_LOSS_MSE = 2,
+  MOLCLR_LOSS_L1 = 3
+};
+
+typedef struct molclr_task_head {
+  int32_t num_layers;
+  int32_t loss;
+  int64_t rows;
+  int64_t dims[MOLCLR_TASK_HEAD_MAX_LAYERS + 1];
+  int32_t act[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  const float* x;
+  int64_t ldx;
+  const float* weight[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  const float* bias[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  float* a[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  const void* target; /* by loss; NULL for MOLCLR_LOSS_NONE */
+  float* loss_out;
+  int32_t* status;
+  int32_t* sync;
+} molclr_task_head;
+
+typedef struct molclr_task_head_grads {
+  const float* gloss; /* device scalar, nullable */
+  const float* dh;    /* [rows, dims[1]], nullable */
+  const float* dpred; /* [rows, dims[L]], nullable */
+  float* dx;          /* [rows, lddx], nullable */
+  int64_t lddx;
+  float* dweight[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  float* dbias[MOLCLR_TASK_HEAD_MAX_LAYERS];
+  int32_t accumulate[MOLCLR_TASK_HEAD_MAX_LAYERS];
+} molclr_task_head_grads;
+
+size_t molclr_task_head_workspace_bytes(const molclr_task_head* head);
+int molclr_task_head_fwd(const molclr_task_head* head, void* workspace, size_t workspace_bytes,
+                         molclr_stream_t stream);
+int molclr_task_head_bwd(const molclr_task_head* head, const molclr_task_head_grads* grads,
+                         void* workspace, size_t workspace_bytes, molclr_stream_t stream);
+
 /* ---- Benchmark instrumentation (no reference counterpart) -------------------
  * Opt-in kernel timer.  While a kind is enabled, its launches go through
  * hipExtLaunchKernelGGL with a start/stop event pair recorded by the dispatch

@@ -6,6 +6,8 @@ Drop-in counterparts of the reference modules (CameronDiao/MolCLR):
 * ``molclr_amd.gcn_molclr.GCN``      <- models/gcn_molclr.py
 * ``molclr_amd.nt_xent.NTXentLoss``  <- utils/nt_xent.py
 * ``molclr_amd.molclr.MolCLR``       <- molclr.py (trainer loop)
+* ``molclr_amd.ginet_finetune.GINet`` / ``gcn_finetune.GCN`` <- models/*_finetune.py
+* ``molclr_amd.finetune.FineTune``   <- finetune.py (supervised fine-tuning)
 
 Every op runs on the HIP kernels of ``libmolclr_hip.so`` (C ABI:
 include/molclr.h), built in-tree by ``python -m molclr_amd.build``.

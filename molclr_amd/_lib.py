@@ -186,6 +186,9 @@ SIGNATURES = {
                                               _P, c_size_t, _P, c_int]),
     "molclr_linear_wgrad_bf16": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, c_int, _P,
                                          c_size_t, _P]),
+    "molclr_task_head_workspace_bytes": (c_size_t, [_P]),
+    "molclr_task_head_fwd": (c_int, [_P, _P, c_size_t, _P]),
+    "molclr_task_head_bwd": (c_int, [_P, _P, _P, c_size_t, _P]),
     "molclr_ktimer_start": (c_int, [c_int]),
     "molclr_ktimer_read": (c_int, [c_int, _P, _P]),
     "molclr_ktimer_stop": (c_int, []),
@@ -198,6 +201,12 @@ MAX_LAYERS = 16
 MAX_SEGMENTS = 8
 DTYPE_F32, DTYPE_BF16 = 0, 1
 STATUS_ATOM_RANGE = 8  # MOLCLR_STATUS_ATOM_RANGE
+STATUS_LABEL_RANGE = 16  # MOLCLR_STATUS_LABEL_RANGE
+TASK_HEAD_MAX_LAYERS = 10
+TASK_HEAD_MAX_CLASSES = 16
+TASK_HEAD_MAX_DIM = 2044
+ACT_NONE, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2
+LOSS_NONE, LOSS_CROSS_ENTROPY, LOSS_MSE, LOSS_L1 = 0, 1, 2, 3
 KTIMER_GINE_AGG = 1
 KTIMER_GEMM = 2
 KTIMER_NTXENT = 4
@@ -244,6 +253,25 @@ class GcnEncoderGrads(ctypes.Structure):
     _fields_ = [("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
         (f, _L16) for f in ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight",
                             "bn_bias")] + [("layer_done", _L16), ("embed_done", c_void_p)]
+
+
+_L10 = c_void_p * 10
+
+
+class TaskHeadC(ctypes.Structure):
+    """struct molclr_task_head."""
+    _fields_ = [("num_layers", ctypes.c_int32), ("loss", ctypes.c_int32), ("rows", c_int64),
+                ("dims", c_int64 * 11), ("act", ctypes.c_int32 * 10), ("x", c_void_p),
+                ("ldx", c_int64), ("weight", _L10), ("bias", _L10), ("a", _L10),
+                ("target", c_void_p), ("loss_out", c_void_p), ("status", c_void_p),
+                ("sync", c_void_p)]
+
+
+class TaskHeadGradsC(ctypes.Structure):
+    """struct molclr_task_head_grads."""
+    _fields_ = [("gloss", c_void_p), ("dh", c_void_p), ("dpred", c_void_p), ("dx", c_void_p),
+                ("lddx", c_int64), ("dweight", _L10), ("dbias", _L10),
+                ("accumulate", ctypes.c_int32 * 10)]
 
 
 class DeviceGraphC(ctypes.Structure):

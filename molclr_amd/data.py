@@ -206,6 +206,9 @@ def raise_for_status(st: int) -> None:
         if st & _lib.STATUS_ATOM_RANGE:
             what.append("atom type / chirality outside the model's embedding tables "
                         "(the reference's nn.Embedding raises IndexError)")
+        if st & _lib.STATUS_LABEL_RANGE:
+            what.append("class label outside [0, number of classes) "
+                        "(the reference's CrossEntropyLoss raises)")
         raise ValueError("invalid graph batch: " + ", ".join(what))
 
 

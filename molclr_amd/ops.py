@@ -1410,3 +1410,185 @@ def nt_xent_pair_normalized(z, batch_size, temperature, use_cosine_similarity=Tr
     _check(z)
     return _NTXentPairNormalized.apply(z, batch_size, temperature, bool(use_cosine_similarity),
                                        group, eps)
+
+
+# ---------------------------------------------------------------------------
+# Supervised task head (fine-tuning): feat_lin + pred_head / pred_lin + loss
+# ---------------------------------------------------------------------------
+# MOLCLR_TASK_HEAD=0 composes the chain from ops.linear, torch activations and
+# a torch loss instead (the fallback, and the benchmark's comparison:
+# tools/bench_finetune.py); tests flip the module switch.
+TASK_HEAD = os.environ.get("MOLCLR_TASK_HEAD", "1") != "0"
+_HEAD_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU,
+              "softplus": _lib.ACT_SOFTPLUS}
+_HEAD_LOSSES = {None: _lib.LOSS_NONE, "none": _lib.LOSS_NONE,
+                "cross_entropy": _lib.LOSS_CROSS_ENTROPY, "mse": _lib.LOSS_MSE,
+                "l1": _lib.LOSS_L1}
+_HEAD_SYNC: dict = {}
+
+
+def _head_sync(dev) -> torch.Tensor:
+    """The forward's ticket word (molclr_task_head.sync): zero between calls,
+    one per device and stream so overlapping calls never share it."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    t = _HEAD_SYNC.get(key)
+    if t is None:
+        t = _HEAD_SYNC[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return t
+
+
+def _head_struct(x, Ws, bs, outs, acts, loss_code, target, loss_out, status, sync):
+    L = len(Ws)
+    c = _lib.TaskHeadC()
+    c.num_layers, c.loss, c.rows = L, loss_code, x.shape[0]
+    c.dims[0] = x.shape[1]
+    for l in range(L):
+        c.dims[l + 1] = Ws[l].shape[0]
+        c.act[l] = acts[l]
+        c.weight[l], c.bias[l], c.a[l] = Ws[l].data_ptr(), bs[l].data_ptr(), outs[l].data_ptr()
+    c.x, c.ldx = x.data_ptr(), x.stride(0)
+    c.target, c.loss_out = _lib.ptr(target), _lib.ptr(loss_out)
+    c.status, c.sync = _lib.ptr(status), _lib.ptr(sync)
+    return c
+
+
+class _TaskHead(torch.autograd.Function):
+    """molclr_task_head_fwd / _bwd: (h, pred, loss) = chain(x) in one launch,
+    the backward in two.  params = W_1..W_L, b_1..b_L."""
+
+    @staticmethod
+    def forward(ctx, x, target, status, loss_code, acts, *params):
+        L = len(acts)
+        Ws = [_c(w) for w in params[:L]]
+        bs = [_c(b) for b in params[L:]]
+        _check(x, target, status, *Ws, *bs)
+        x = _c(x)
+        dev, B = x.device, x.shape[0]
+        outs = [torch.empty(B, w.shape[0], dtype=torch.float32, device=dev) for w in Ws]
+        loss = torch.empty((), dtype=torch.float32, device=dev) if loss_code else None
+        c = _head_struct(x, Ws, bs, outs, acts, loss_code, target, loss, status,
+                         _head_sync(dev) if loss_code else None)
+        ws_bytes = _lib.query("molclr_task_head_workspace_bytes", ctypes.addressof(c))
+        ws = _ws(ws_bytes, dev)
+        _lib.call("molclr_task_head_fwd", ctypes.addressof(c), ws.data_ptr(), ws_bytes, _stream(x))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, target, *Ws, *bs, *outs)
+        ctx.params = params
+        ctx.acts, ctx.loss_code = acts, loss_code
+        h = outs[0]
+        pred = outs[-1] if L > 1 else h.clone()  # two outputs are two tensors
+        return h, pred, loss
+
+    @staticmethod
+    def backward(ctx, dh, dpred, dloss):
+        L = len(ctx.acts)
+        saved = ctx.saved_tensors
+        x, target = saved[0], saved[1]
+        Ws, bs, outs = saved[2:2 + L], saved[2 + L:2 + 2 * L], saved[2 + 2 * L:]
+        dev, need = x.device, ctx.needs_input_grad
+        dh = None if dh is None else _c(dh)
+        dpred = None if dpred is None else _c(dpred)
+        gloss = None
+        if dloss is not None and ctx.loss_code:
+            gloss = dloss.to(torch.float32).contiguous()
+        c = _head_struct(x, Ws, bs, outs, ctx.acts, ctx.loss_code, target, None, None, None)
+        g = _lib.TaskHeadGradsC()
+        g.gloss, g.dh, g.dpred = _lib.ptr(gloss), _lib.ptr(dh), _lib.ptr(dpred)
+        dx = torch.empty_like(x) if need[0] else None
+        g.dx, g.lddx = _lib.ptr(dx), x.shape[1]
+        dWs, dbs, keep = [None] * L, [None] * L, []
+        for l in range(L):
+            nw, nb = need[5 + l], need[5 + L + l]
+            pW, pb = ctx.params[l], ctx.params[L + l]
+            wbuf = bbuf = None
+            wacc = bacc = 0
+            if nw:
+                wbuf, wacc, dWs[l] = _grad_sink(pW, Ws[l].shape, dev)
+            if nb:
+                bbuf, bacc, dbs[l] = _grad_sink(pb, bs[l].shape, dev)
+            if nw and nb and wacc != bacc:  # mixed ownership: fresh buffers for both
+                wbuf, wacc, dWs[l] = _grad_sink(None, Ws[l].shape, dev)
+                bbuf, bacc, dbs[l] = _grad_sink(None, bs[l].shape, dev)
+            g.dweight[l], g.dbias[l] = _lib.ptr(wbuf), _lib.ptr(bbuf)
+            g.accumulate[l] = wacc if nw else bacc
+            keep += [wbuf, bbuf]
+        ws_bytes = _lib.query("molclr_task_head_workspace_bytes", ctypes.addressof(c))
+        ws = _ws(ws_bytes, dev)
+        _lib.call("molclr_task_head_bwd", ctypes.addressof(c), ctypes.addressof(g), ws.data_ptr(),
+                  ws_bytes, _stream(x))
+        return (dx, None, None, None, None, *dWs, *dbs)
+
+
+def _task_head_composed(x, weights, biases, acts, loss_code, target, status):
+    """The same chain from ops.linear, torch activations and a torch loss."""
+    F = torch.nn.functional
+    a, h = x, None
+    for l, (W, b) in enumerate(zip(weights, biases)):
+        # ops.linear's GEMMs take widths that are multiples of 4; the others
+        # (the 2- or 1-wide output layer, an odd feat_dim // 2) go to torch
+        if W.shape[0] % 4 == 0 and W.shape[1] % 4 == 0:
+            a = linear(a, W, b)
+        else:
+            a = F.linear(a, W, b)
+        if acts[l] == _lib.ACT_RELU:
+            a = torch.relu(a)
+        elif acts[l] == _lib.ACT_SOFTPLUS:
+            a = F.softplus(a)
+        if l == 0:
+            h = a
+    pred, loss = a, None
+    if loss_code == _lib.LOSS_CROSS_ENTROPY:
+        C = pred.shape[1]
+        bad = (target < 0) | (target >= C)  # never an index: clamped, its row NaN
+        if status is not None:
+            status.bitwise_or_((bad.any() * _lib.STATUS_LABEL_RANGE).to(torch.int32))
+        rows = F.cross_entropy(pred, target.clamp(0, C - 1), reduction="none")
+        loss = torch.where(bad, torch.full_like(rows, float("nan")), rows).mean()
+    elif loss_code == _lib.LOSS_MSE:
+        loss = F.mse_loss(pred, target)
+    elif loss_code == _lib.LOSS_L1:
+        loss = F.l1_loss(pred, target)
+    return h, pred, loss
+
+
+def task_head_fused(dims) -> bool:
+    """Whether a chain of these widths runs through the fused kernels: the
+    switch is on and every width fits their LDS row block.  Wider chains (a
+    feat_dim or emb_dim above _lib.TASK_HEAD_MAX_DIM) take the composed path."""
+    return TASK_HEAD and max(dims) <= _lib.TASK_HEAD_MAX_DIM
+
+
+def task_head(x, weights, biases, acts, loss=None, target=None, status=None):
+    """The fine-tuning readout after the pooling, ``(h, pred, loss)``:
+    ``a_l = act_l(a_{l-1} W_l^T + b_l)`` over ``weights`` / ``biases``
+    (nn.Linear layout), ``acts`` in {None, 'relu', 'softplus'} per layer,
+    ``h = a_1``, ``pred = a_L`` and ``loss`` in {None, 'cross_entropy', 'mse',
+    'l1'} on ``pred`` against ``target`` (int64 [B] labels, or floats
+    [B, d_L]); ``loss`` is None without one.  A label outside [0, d_L) sets
+    STATUS_LABEL_RANGE in ``status`` (an int32 device word, e.g. the batch's
+    graph status) and makes the loss NaN; nothing here synchronises.  Chains
+    the fused kernels do not take (task_head_fused) are composed from
+    ops.linear, torch activations and a torch loss."""
+    L = len(weights)
+    if not 1 <= L <= _lib.TASK_HEAD_MAX_LAYERS or len(biases) != L or len(acts) != L:
+        raise ValueError(f"task_head: {L} layers (1..{_lib.TASK_HEAD_MAX_LAYERS}), one bias and "
+                         "one activation each")
+    acts = tuple(_HEAD_ACTS[a] for a in acts)
+    loss_code = _HEAD_LOSSES[loss]
+    B, C = x.shape[0], weights[-1].shape[0]
+    if loss_code:
+        if target is None:
+            raise ValueError("task_head: the loss needs a target")
+        if loss_code == _lib.LOSS_CROSS_ENTROPY:
+            if C > _lib.TASK_HEAD_MAX_CLASSES:
+                raise ValueError(f"task_head: cross-entropy over {C} classes "
+                                 f"(at most {_lib.TASK_HEAD_MAX_CLASSES})")
+            target = _c(target.reshape(B).to(torch.long))
+        else:
+            target = _c(target.reshape(B, C).to(torch.float32))
+    else:
+        target = None
+    _check(x, target, status)
+    if not task_head_fused([x.shape[1]] + [W.shape[0] for W in weights]):
+        return _task_head_composed(x, weights, biases, acts, loss_code, target, status)
+    return _TaskHead.apply(x, target, status, loss_code, acts, *weights, *biases)

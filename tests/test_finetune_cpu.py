@@ -1,0 +1,216 @@
+"""Fine-tuning pieces that need no GPU: the models' parameter layout against
+the reference's (oracle.finetune_ref), load_my_state_dict, the Normalizer, the
+numpy metrics, and the labelled CSV dataset with its split."""
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from molclr_amd import finetune as ft
+from molclr_amd import gcn_finetune, gcn_molclr, ginet_finetune, ginet_molclr
+from molclr_amd.dataset_test import (MolTestDataset, MolTestDatasetWrapper, collate_labelled,
+                                     read_smiles)
+from oracle.finetune_ref import FinetuneGCNLayout, FinetuneGINetLayout
+
+
+def _shapes(m):
+    return {k: tuple(v.shape) for k, v in m.state_dict().items()}
+
+
+@pytest.mark.parametrize("task,n_layer,act", list(itertools.product(
+    ("classification", "regression"), (1, 2, 3), ("softplus", "relu"))))
+def test_ginet_state_dict_matches_reference_layout(task, n_layer, act):
+    kw = dict(num_layer=2, emb_dim=12, feat_dim=10, pred_n_layer=n_layer, pred_act=act)
+    ours = ginet_finetune.GINet(task, drop_ratio=0.1, pool='add', **kw)
+    ref = FinetuneGINetLayout(task, **kw)
+    assert list(ours.state_dict()) == list(ref.state_dict())
+    assert _shapes(ours) == _shapes(ref)
+    assert not any(k.startswith("out_lin") for k in ours.state_dict())
+
+
+@pytest.mark.parametrize("task", ("classification", "regression"))
+def test_gcn_state_dict_matches_reference_layout(task):
+    ours = gcn_finetune.GCN(task, num_layer=3, emb_dim=12, feat_dim=10)
+    ref = FinetuneGCNLayout(task, num_layer=3, emb_dim=12, feat_dim=10)
+    assert list(ours.state_dict()) == list(ref.state_dict())
+    assert _shapes(ours) == _shapes(ref)
+
+
+def test_constructor_errors():
+    with pytest.raises(ValueError):
+        ginet_finetune.GINet(pred_act='gelu', num_layer=1, emb_dim=8, feat_dim=8)
+    with pytest.raises(ValueError):
+        ginet_finetune.GINet('ranking', num_layer=1, emb_dim=8, feat_dim=8)
+    with pytest.raises(ValueError):
+        gcn_finetune.GCN(num_layer=1, emb_dim=8, feat_dim=8)
+
+
+def test_seeded_initialisation_follows_creation_order():
+    """feat_lin and the head are drawn right after the encoder: the same seed
+    gives the parameters of a torch model built in the reference's order."""
+    torch.manual_seed(5)
+    ours = ginet_finetune.GINet('regression', num_layer=1, emb_dim=8, feat_dim=6)
+    torch.manual_seed(5)
+    enc = ginet_molclr.GINet(num_layer=1, emb_dim=8, feat_dim=6)
+    # identical up to feat_lin (the pre-training class draws out_lin after it)
+    for k in ("x_embedding1.weight", "gnns.0.mlp.2.weight", "feat_lin.weight", "feat_lin.bias"):
+        assert torch.equal(ours.state_dict()[k], enc.state_dict()[k]), k
+
+
+@pytest.mark.parametrize("kind", ("gin", "gcn"))
+def test_subclass_sets_what_the_parent_init_sets(kind):
+    """The fine-tuning classes restate the parent's __init__ (they must not
+    create out_lin): every attribute and submodule the parent sets, except
+    out_lin, is there with the same value."""
+    if kind == "gin":
+        parent = ginet_molclr.GINet(2, 12, 10, 0.2, 'add')
+        child = ginet_finetune.GINet('regression', 2, 12, 10, 0.2, 'add')
+    else:
+        parent = gcn_molclr.GCN(2, 12, 10, 0.2, 'add')
+        child = gcn_finetune.GCN('regression', 2, 12, 10, 0.2, 'add')
+    plain = {k: v for k, v in vars(parent).items() if not k.startswith('_')}
+    assert plain and {k: getattr(child, k, None) for k in plain} == plain
+    mods = {n for n, _ in parent.named_children()} - {"out_lin"}
+    assert mods <= {n for n, _ in child.named_children()}
+    assert "out_lin" not in dict(child.named_children())
+
+
+@pytest.mark.parametrize("kind", ("gin", "gcn"))
+def test_load_my_state_dict(kind):
+    torch.manual_seed(1)
+    if kind == "gin":
+        pre = ginet_molclr.GINet(num_layer=2, emb_dim=12, feat_dim=10)
+        model = ginet_finetune.GINet('classification', num_layer=2, emb_dim=12, feat_dim=10)
+        head = "pred_head."
+    else:
+        pre = gcn_molclr.GCN(num_layer=2, emb_dim=12, feat_dim=10)
+        model = gcn_finetune.GCN('classification', num_layer=2, emb_dim=12, feat_dim=10)
+        head = "pred_lin."
+    for bn in pre.batch_norms:  # non-trivial buffers
+        bn.running_mean.uniform_(-1, 1)
+        bn.num_batches_tracked.fill_(7)
+    before = {k: v.clone() for k, v in model.state_dict().items()}
+    sd = pre.state_dict()
+    assert any(k.startswith("out_lin.") for k in sd)
+    model.load_my_state_dict(sd)
+    after = model.state_dict()
+    for k, v in after.items():
+        if k.startswith(head):
+            assert torch.equal(v, before[k]), k  # untouched
+        else:
+            assert torch.equal(v, sd[k]), k
+    assert not any(k.startswith("out_lin.") for k in after)
+    # Parameters (not only tensors) are accepted, a shape mismatch raises
+    model.load_my_state_dict({"feat_lin.bias": torch.nn.Parameter(torch.ones(10))})
+    assert torch.equal(model.feat_lin.bias.data, torch.ones(10))
+    with pytest.raises(RuntimeError):
+        model.load_my_state_dict({"feat_lin.bias": torch.ones(11)})
+
+
+def test_normalizer_round_trip():
+    g = torch.Generator().manual_seed(0)
+    y = torch.randn(50, 1, generator=g) * 7.0 - 3.0
+    n = ft.Normalizer(y)
+    z = n.norm(y)
+    assert abs(z.mean().item()) < 1e-5 and abs(z.std().item() - 1.0) < 1e-5
+    assert torch.allclose(n.denorm(z), y, rtol=1e-5, atol=1e-5)
+    m = ft.Normalizer(torch.zeros(3))
+    m.load_state_dict(n.state_dict())
+    assert torch.equal(m.norm(y), z)
+
+
+def test_metrics_hand_computed():
+    # scores 0.1 0.4 0.35 0.8, labels 0 0 1 1: 3 of 4 (pos, neg) pairs ordered
+    assert ft.roc_auc_score([0, 0, 1, 1], [0.1, 0.4, 0.35, 0.8]) == pytest.approx(0.75)
+    # ties count half: pairs (p=0.5 vs n=0.5) 0.5, (0.5 vs 0.2) 1, (0.9 vs both) 2 -> 3.5 / 4
+    assert ft.roc_auc_score([1, 0, 0, 1], [0.5, 0.5, 0.2, 0.9]) == pytest.approx(0.875)
+    # all scores tied: 0.5
+    assert ft.roc_auc_score([1, 0, 1, 0, 0], [2.0] * 5) == pytest.approx(0.5)
+    assert ft.roc_auc_score([0, 1], [1.0, 0.0]) == 0.0
+    with pytest.raises(ValueError):
+        ft.roc_auc_score([1, 1], [0.1, 0.2])
+    assert ft.rmse_score([1.0, 2.0, 3.0], [[1.0], [4.0], [1.0]]) == pytest.approx((8 / 3) ** 0.5)
+    assert ft.mae_score([1.0, 2.0, 3.0], [[1.0], [4.0], [0.0]]) == pytest.approx(5 / 3)
+
+
+def test_metrics_against_sklearn():
+    skm = pytest.importorskip("sklearn.metrics")
+    rng = np.random.default_rng(0)
+    y = rng.integers(0, 2, 300)
+    s = np.round(rng.normal(size=300) + y, 1)  # rounded: many ties
+    assert ft.roc_auc_score(y, s) == pytest.approx(skm.roc_auc_score(y, s), abs=1e-12)
+    t, p = rng.normal(size=100), rng.normal(size=100)
+    assert ft.rmse_score(t, p) == pytest.approx(skm.mean_squared_error(t, p) ** 0.5, rel=1e-12)
+    assert ft.mae_score(t, p) == pytest.approx(skm.mean_absolute_error(t, p), rel=1e-12)
+
+
+ROWS = [("C", "1"),            # the first data row: skipped as the reference skips it
+        ("CCO", "1"), ("c1ccccc1", "0"), ("CC(=O)O", ""),      # empty label
+        ("C1CC", "1"),         # unclosed ring: unparsable
+        ("CCN", "0"), ("C[C@H](N)C(=O)O", "1"), ("CC#N", "0"), ("OCC", "1"), ("CCCC", "0"),
+        ("CNC", "1"), ("CCOC", "0")]
+
+
+def _write_csv(path, rows, header=("smiles", "label", "other")):
+    with open(path, "w") as f:
+        f.write(",".join(header) + "\n")
+        for s, l in rows:
+            f.write(f"{s},{l},x\n")
+    return str(path)
+
+
+def test_read_smiles_and_dataset(tmp_path):
+    path = _write_csv(tmp_path / "toy.csv", ROWS)
+    smiles, labels = read_smiles(path, "label", "classification")
+    assert smiles == ["CCO", "c1ccccc1", "CCN", "C[C@H](N)C(=O)O", "CC#N", "OCC", "CCCC", "CNC",
+                      "CCOC"]
+    assert labels == [1, 0, 0, 1, 0, 1, 0, 1, 0]
+    _, flabels = read_smiles(path, "label", "regression")
+    assert flabels == [float(v) for v in labels]
+    with pytest.raises(ValueError):
+        read_smiles(path, "label", "ranking")
+
+    ds = MolTestDataset(path, "label", "classification")
+    d = ds[0]  # ethanol with explicit hydrogens: 3 heavy atoms + 6 H, 8 bonds
+    assert d.x.shape == (9, 2) and d.edge_index.shape == (2, 16) and d.edge_attr.shape == (16, 2)
+    assert d.y.shape == (1, 1) and d.y.dtype == torch.long and d.y.item() == 1
+    r = MolTestDataset(path, "label", "regression")[1]
+    assert r.y.shape == (1, 1) and r.y.dtype == torch.float32
+    b = collate_labelled([ds[0], ds[1], ds[2]])
+    assert b.y.shape == (3, 1) and b.y.flatten().tolist() == [1, 0, 0]
+    assert b.num_graphs == 3 and b.mol_index.tolist() == [0, 1, 2]
+    assert b.x.shape[0] == sum(ds[i].x.shape[0] for i in range(3))
+
+
+def test_qm9_unit_conversion(tmp_path):
+    (tmp_path / "qm9").mkdir()
+    path = _write_csv(tmp_path / "qm9" / "qm9.csv", [("C", "0"), ("CC", "0.5")],
+                      header=("smiles", "homo", "mu"))
+    d = MolTestDataset(path, "homo", "regression")[0]
+    assert d.y.item() == pytest.approx(0.5 * 27.211386246)
+
+
+def test_random_split_is_disjoint_and_complete(tmp_path):
+    rows = [("C", "0")] + [("C" * (1 + i % 7), str(i % 2)) for i in range(53)]
+    path = _write_csv(tmp_path / "toy.csv", rows)
+    w = MolTestDatasetWrapper(8, 0, 0.1, 0.2, "classification", path, "label", "random", seed=3)
+    tr, va, te = w.split_indices(53)
+    assert len(va) == 5 and len(te) == 10 and len(tr) == 38
+    assert sorted(tr + va + te) == list(range(53))
+    assert w.split_indices(53) == (tr, va, te)  # seeded
+    smiles, train, valid, test = w.get_data_loaders()
+    assert len(smiles) == 53
+    seen = []
+    for loader in (train, valid, test):
+        for batch in loader:
+            assert batch.y.shape == (batch.num_graphs, 1)
+            seen += batch.mol_index.tolist()
+    assert sorted(seen) == list(range(53))
+
+
+def test_scaffold_split_raises(tmp_path):
+    path = _write_csv(tmp_path / "toy.csv", ROWS)
+    w = MolTestDatasetWrapper(4, 0, 0.1, 0.1, "classification", path, "label", "scaffold")
+    with pytest.raises(NotImplementedError, match="Murcko"):
+        w.get_data_loaders()

@@ -1,0 +1,131 @@
+"""Fine-tuning step and task-head timings: the fused head (task_head.hip)
+against the composed one (MOLCLR_TASK_HEAD=0: ops.linear per layer, torch
+activations and loss).
+
+GIN 5 x 300, feat_dim 512, pred_n_layer 2, softplus, classification, synthetic
+molecules; batches of 32 and 256, drop_ratio 0 and 0.3.  Each configuration
+times the whole step (zero_grad, model.loss, backward, FusedAdam) and the head
+alone (forward + backward on pooled features, gradients accumulating into
+FusedAdam's buffer, nothing else launched), the two head paths alternating
+round by round in one process so drift hits both alike.  Per round: `iters`
+back-to-back iterations between two device syncs, wall-clock per iteration;
+reported are the median over rounds and the spread (min .. max).  Kernel
+launches per iteration are counted with the torch profiler.
+
+    python tools/bench_finetune.py [--rounds 9] [--iters 50] [--out FILE]
+prints one JSON line per configuration.
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from molclr_amd import ops  # noqa: E402
+from molclr_amd.dataset import collate_views, random_molecule  # noqa: E402
+from molclr_amd.ginet_finetune import GINet  # noqa: E402
+from molclr_amd.optim import FusedAdam  # noqa: E402
+
+
+def batches(B, n, dev, seed=0):
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        mols = [random_molecule(rng, "pubchem") for _ in range(B)]
+        b = collate_views([(m.x, m.edge_index, m.edge_attr) for m in mols]).to(dev)
+        out.append((b, torch.from_numpy(rng.integers(0, 2, B)).to(dev)))
+    return out
+
+
+def timed(fn, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(iters):
+        fn(i)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e6
+
+
+def launches(fn):
+    from torch.profiler import ProfilerActivity, profile
+    fn(0)
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn(0)
+        torch.cuda.synchronize()
+    return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+               and "memcpy" not in e.name.lower() and "memset" not in e.name.lower())
+
+
+def summary(xs):
+    return {"median_us": round(statistics.median(xs), 1), "min_us": round(min(xs), 1),
+            "max_us": round(max(xs), 1)}
+
+
+def run(B, drop, rounds, iters, dev):
+    torch.manual_seed(0)
+    model = GINet("classification", 5, 300, 512, drop, "mean", 2, "softplus").to(dev)
+    model.train()
+    opt = FusedAdam(model.parameters(), 1e-4, weight_decay=1e-6)
+    data = batches(B, 8, dev)
+
+    def step(i):
+        b, y = data[i % len(data)]
+        opt.zero_grad()
+        model.loss(b, y)[2].backward()
+        opt.step()
+
+    lins, acts = model._head_layers()
+    Ws = [model.feat_lin.weight] + [m.weight for m in lins]
+    bs = [model.feat_lin.bias] + [m.bias for m in lins]
+    pooled = torch.randn(B, 300, device=dev, requires_grad=True)
+    y0 = data[0][1]
+
+    def head(i):  # the head's launches alone: no zero_grad, no input-gradient accumulation
+        pooled.grad = None
+        ops.task_head(pooled, Ws, bs, [None] + acts, "cross_entropy", y0)[2].backward()
+
+    res = {"batch": B, "drop_ratio": drop, "rounds": rounds, "iters": iters}
+    times = {(w, f): [] for w in ("step", "head") for f in (1, 0)}
+    for fused in (1, 0):
+        ops.TASK_HEAD = bool(fused)
+        timed(step, 10)
+        timed(head, 10)
+        res[f"launches_step_fused{fused}"] = launches(step)
+        res[f"launches_head_fused{fused}"] = launches(head)
+    for _ in range(rounds):
+        for fused in (1, 0):  # alternate the two paths round by round
+            ops.TASK_HEAD = bool(fused)
+            times[("step", fused)].append(timed(step, iters))
+            times[("head", fused)].append(timed(head, iters))
+    ops.TASK_HEAD = True
+    for (w, f), xs in times.items():
+        res[f"{w}_fused{f}"] = summary(xs)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lines = []
+    for B in (32, 256):
+        for drop in (0.0, 0.3):
+            lines.append(json.dumps(run(B, drop, a.rounds, a.iters, dev)))
+            print(lines[-1], flush=True)
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
