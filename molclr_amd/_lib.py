@@ -217,42 +217,51 @@ AUG_SUBGRAPH, AUG_MIX = 0, 1
 _L16 = c_void_p * 16
 
 
+# Per-layer parameter fields of the encoder structs, in the order the executors
+# (and the models' _encoder_params) take them; the structs below, the
+# backward's gradient fill and ops.*_PARAMS_PER_LAYER derive from these.
+GIN_LAYER_PARAMS = ("mlp0_weight", "mlp0_bias", "mlp2_weight", "mlp2_bias", "edge_embedding1",
+                    "edge_embedding2", "bn_weight", "bn_bias")
+GCN_LAYER_PARAMS = ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight", "bn_bias")
+
+
+def _encoder_fields(layer_params, planes, tail):
+    """struct molclr_{gin,gcn}_encoder: the common head, the per-layer
+    parameter, BatchNorm-buffer and weight-plane pointers, the kind's tail."""
+    return [("num_layer", ctypes.c_int32), ("training", ctypes.c_int32), ("dim", c_int64),
+            ("n_atom", c_int64), ("n_chiral", c_int64), ("momentum", c_double),
+            ("eps", c_double), ("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
+        (f, _L16) for f in layer_params + ("bn_running_mean", "bn_running_var",
+                                           "bn_num_batches_tracked") + planes] + tail + [
+        ("fp32_gemm", ctypes.c_int32), ("status", c_void_p)]
+
+
+def _encoder_grads_fields(layer_params):
+    """struct molclr_{gin,gcn}_encoder_grads."""
+    return [("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
+        (f, _L16) for f in layer_params] + [("layer_done", _L16), ("embed_done", c_void_p)]
+
+
 class GinEncoder(ctypes.Structure):
     """struct molclr_gin_encoder (include/molclr.h)."""
-    _fields_ = [("num_layer", ctypes.c_int32), ("training", ctypes.c_int32), ("dim", c_int64),
-                ("n_atom", c_int64), ("n_chiral", c_int64), ("momentum", c_double),
-                ("eps", c_double), ("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
-        (f, _L16) for f in ("mlp0_weight", "mlp0_bias", "mlp2_weight", "mlp2_bias",
-                            "edge_embedding1", "edge_embedding2", "bn_weight", "bn_bias",
-                            "bn_running_mean", "bn_running_var", "bn_num_batches_tracked",
-                            "mlp0_planes", "mlp0_planes_t", "mlp2_planes", "mlp2_planes_t")] + [
-        ("dtype", ctypes.c_int32), ("fp32_gemm", ctypes.c_int32), ("status", c_void_p)]
+    _fields_ = _encoder_fields(
+        GIN_LAYER_PARAMS, ("mlp0_planes", "mlp0_planes_t", "mlp2_planes", "mlp2_planes_t"),
+        [("dtype", ctypes.c_int32)])
 
 
 class GinEncoderGrads(ctypes.Structure):
     """struct molclr_gin_encoder_grads."""
-    _fields_ = [("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
-        (f, _L16) for f in ("mlp0_weight", "mlp0_bias", "mlp2_weight", "mlp2_bias",
-                            "edge_embedding1", "edge_embedding2", "bn_weight", "bn_bias")] + [
-        ("layer_done", _L16), ("embed_done", c_void_p)]
+    _fields_ = _encoder_grads_fields(GIN_LAYER_PARAMS)
 
 
 class GcnEncoder(ctypes.Structure):
     """struct molclr_gcn_encoder (include/molclr.h)."""
-    _fields_ = [("num_layer", ctypes.c_int32), ("training", ctypes.c_int32), ("dim", c_int64),
-                ("n_atom", c_int64), ("n_chiral", c_int64), ("momentum", c_double),
-                ("eps", c_double), ("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
-        (f, _L16) for f in ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight",
-                            "bn_bias", "bn_running_mean", "bn_running_var",
-                            "bn_num_batches_tracked", "weight_planes", "weight_planes_t")] + [
-        ("fp32_gemm", ctypes.c_int32), ("status", c_void_p)]
+    _fields_ = _encoder_fields(GCN_LAYER_PARAMS, ("weight_planes", "weight_planes_t"), [])
 
 
 class GcnEncoderGrads(ctypes.Structure):
     """struct molclr_gcn_encoder_grads."""
-    _fields_ = [("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
-        (f, _L16) for f in ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight",
-                            "bn_bias")] + [("layer_done", _L16), ("embed_done", c_void_p)]
+    _fields_ = _encoder_grads_fields(GCN_LAYER_PARAMS)
 
 
 _L10 = c_void_p * 10

@@ -12,7 +12,7 @@ from __future__ import annotations
 from torch import nn
 
 from . import gcn_molclr
-from .gcn_molclr import GCNConv, num_atom_type, num_chirality_tag
+from .gcn_molclr import GCNConv, num_atom_type, num_chirality_tag  # noqa: F401
 from .ginet_finetune import FinetuneReadout, task_out_dim
 
 
@@ -22,39 +22,11 @@ class GCN(FinetuneReadout, gcn_molclr.GCN):
     def __init__(self, task='classification', num_layer=5, emb_dim=300, feat_dim=256,
                  drop_ratio=0, pool='mean'):
         # The parent's __init__ is NOT called (it would create out_lin, see
-        # ginet_finetune.GINet).  COUPLING: whatever gcn_molclr.GCN.__init__
-        # sets that its encoder methods read must be set here too;
-        # tests/test_finetune_cpu.py compares the two classes' attributes.
+        # ginet_finetune.GINet).
         nn.Module.__init__(self)
-        self.num_layer = num_layer
-        self.emb_dim = emb_dim
-        self.feat_dim = feat_dim
-        self.drop_ratio = drop_ratio
         self.task = task
         out_dim = task_out_dim(task)
-
-        if self.num_layer < 2:
-            raise ValueError("Number of GNN layers must be greater than 1.")
-
-        self.x_embedding1 = nn.Embedding(num_atom_type, emb_dim)
-        self.x_embedding2 = nn.Embedding(num_chirality_tag, emb_dim)
-        nn.init.xavier_uniform_(self.x_embedding1.weight.data)
-        nn.init.xavier_uniform_(self.x_embedding2.weight.data)
-
-        self.gnns = nn.ModuleList()
-        for _ in range(num_layer):
-            self.gnns.append(GCNConv(emb_dim, aggr="add"))
-
-        self.batch_norms = nn.ModuleList()
-        for _ in range(num_layer):
-            self.batch_norms.append(nn.BatchNorm1d(emb_dim))
-
-        if pool in ('mean', 'add', 'max'):
-            self.pool = pool
-        else:
-            raise ValueError('Not defined pooling!')
-
-        self.feat_lin = nn.Linear(self.emb_dim, self.feat_dim)
+        self._init_encoder(num_layer, emb_dim, feat_dim, drop_ratio, pool)
 
         self.pred_lin = nn.Sequential(
             nn.Linear(self.feat_dim, self.feat_dim // 2),

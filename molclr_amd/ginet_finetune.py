@@ -15,11 +15,9 @@ criterion -- is ONE ops.task_head call (task_head.hip).
 """
 from __future__ import annotations
 
-import torch.nn.functional as F
 from torch import nn
 
 from . import ginet_molclr, ops
-from .data import device_graph
 from .ginet_molclr import (GINEConv, num_atom_type, num_bond_direction,  # noqa: F401
                            num_bond_type, num_chirality_tag)
 
@@ -40,15 +38,8 @@ class FinetuneReadout:
         raise NotImplementedError
 
     def _task(self, data, loss=None, target=None):
-        graph = device_graph(data)
-        if self._executor_ok():  # keep the padded width into the readout
-            h = self._run_encoder(data.x, graph)
-        else:
-            h, graph = self.encode(data, graph)
-        h = ops.segment_pool(h, graph, self.pool)
-        W = self.feat_lin.weight
-        if h.shape[1] != W.shape[1]:  # padded width: zero weight columns for the pads
-            W = F.pad(W, (0, h.shape[1] - W.shape[1]))
+        h, graph = self._embed(data)
+        h, W = self._pool(h, graph)
         lins, acts = self._head_layers()
         return ops.task_head(h, [W] + [m.weight for m in lins],
                              [self.feat_lin.bias] + [m.bias for m in lins], [None] + acts,
@@ -91,41 +82,12 @@ class GINet(FinetuneReadout, ginet_molclr.GINet):
                  precision='fp32'):
         # The parent's __init__ is NOT called: it would create out_lin, whose
         # initialisation draws from the RNG between feat_lin and pred_head and
-        # whose keys the fine-tuning state_dict must not have.  The encoder's
-        # modules and attributes are therefore restated here in the reference's
-        # creation order.  COUPLING: whatever ginet_molclr.GINet.__init__ sets
-        # that its encoder methods read (precision, num_layer, emb_dim,
-        # drop_ratio, pool, the module lists) must be set here too;
-        # tests/test_finetune_cpu.py compares the two classes' attributes.
+        # whose keys the fine-tuning state_dict must not have.
         nn.Module.__init__(self)
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError(f"precision {precision!r}: 'fp32' or 'bf16'")
-        self.precision = precision
-        self.num_layer = num_layer
-        self.emb_dim = emb_dim
-        self.feat_dim = feat_dim
-        self.drop_ratio = drop_ratio
+        self.precision = ginet_molclr.check_precision(precision)
         self.task = task
         out_dim = task_out_dim(task)
-
-        self.x_embedding1 = nn.Embedding(num_atom_type, emb_dim)
-        self.x_embedding2 = nn.Embedding(num_chirality_tag, emb_dim)
-        nn.init.xavier_uniform_(self.x_embedding1.weight.data)
-        nn.init.xavier_uniform_(self.x_embedding2.weight.data)
-
-        self.gnns = nn.ModuleList()
-        for _ in range(num_layer):
-            self.gnns.append(GINEConv(emb_dim))
-
-        self.batch_norms = nn.ModuleList()
-        for _ in range(num_layer):
-            self.batch_norms.append(nn.BatchNorm1d(emb_dim))
-
-        if pool not in ('mean', 'add', 'max'):
-            raise ValueError('Not defined pooling!')
-        self.pool = pool
-
-        self.feat_lin = nn.Linear(self.emb_dim, self.feat_dim)
+        self._init_encoder(num_layer, emb_dim, feat_dim, drop_ratio, pool)
 
         self.pred_n_layer = max(1, pred_n_layer)
         if pred_act == 'relu':

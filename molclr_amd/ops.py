@@ -26,6 +26,7 @@ import torch
 
 import contextlib
 import ctypes
+import dataclasses
 import os
 import functools
 import weakref
@@ -1105,225 +1106,175 @@ class _NTXentPairNormalized(torch.autograd.Function):
         return dz, None, None, None, None, None
 
 
-GIN_PARAMS_PER_LAYER = 8  # mlp0.W, mlp0.b, mlp2.W, mlp2.b, edge_emb1, edge_emb2, bn.W, bn.b
-
-
-class _GINEncoder(torch.autograd.Function):
-    """The whole GINet node-embedding stack (ginet_molclr.py:98-111) through
-    molclr_gin_encoder_fwd / _bwd (encoder.hip): the same kernels as the
-    per-op path in the same order, one host call each way.
-    params: x_embedding1, x_embedding2, then per layer GIN_PARAMS_PER_LAYER."""
-
-    @staticmethod
-    def forward(ctx, x_idx, graph: DeviceGraph, bns, dtype, *params):
-        _check(x_idx, *params)
-        L = len(bns)
-        D = params[0].shape[1]
-        x_idx = _c(x_idx.to(torch.long))
-        N = graph.num_nodes
-        training = bool(bns[0].training)
-        enc = _lib.GinEncoder()
-        enc.num_layer, enc.training, enc.dim = L, int(training), D
-        enc.dtype = dtype
-        # fp32: the GEMM form ops._MLP would use on these shapes (identical kernels)
-        h3 = dtype == _lib.DTYPE_F32 and h3_ok(N, D)
-        kind = "h3" if h3 and H3_FORWARD else "x6"
-        kind_t = "h3" if h3 else "x6"
-        enc.fp32_gemm = (1 | (2 if H3_FORWARD else 0)) if h3 else 0
-        enc.status = graph.status.data_ptr()  # out-of-vocabulary atoms: MOLCLR_STATUS_ATOM_RANGE
-        enc.n_atom, enc.n_chiral = params[0].shape[0], params[1].shape[0]
-        enc.momentum, enc.eps = float(bns[0].momentum), float(bns[0].eps)
-        enc.x_embedding1, enc.x_embedding2 = params[0].data_ptr(), params[1].data_ptr()
-        for l in range(L):
-            W0, b0, W2, b2, E1, E2, g, b = params[2 + GIN_PARAMS_PER_LAYER * l:
-                                                  2 + GIN_PARAMS_PER_LAYER * (l + 1)]
-            bn = bns[l]
-            enc.mlp0_weight[l], enc.mlp0_bias[l] = W0.data_ptr(), b0.data_ptr()
-            enc.mlp2_weight[l], enc.mlp2_bias[l] = W2.data_ptr(), b2.data_ptr()
-            enc.edge_embedding1[l], enc.edge_embedding2[l] = E1.data_ptr(), E2.data_ptr()
-            enc.bn_weight[l], enc.bn_bias[l] = g.data_ptr(), b.data_ptr()
-            enc.bn_running_mean[l] = bn.running_mean.data_ptr()
-            enc.bn_running_var[l] = bn.running_var.data_ptr()
-            nbt = bn.num_batches_tracked
-            enc.bn_num_batches_tracked[l] = nbt.data_ptr() if training and nbt is not None else None
-            twoD = W0.shape[0]
-            # the same planes (and cache entries) ops.linear_fwd / linear_bwd use
-            enc.mlp0_planes[l] = weight_planes(W0, twoD, D, D, 0, kind).data_ptr()
-            enc.mlp0_planes_t[l] = weight_planes(W0, D, twoD, D, 1, kind_t).data_ptr()
-            enc.mlp2_planes[l] = weight_planes(W2, D, twoD, twoD, 0, kind).data_ptr()
-            enc.mlp2_planes_t[l] = weight_planes(W2, twoD, D, twoD, 1, kind_t).data_ptr()
-        dev = x_idx.device
-        arena_bytes = _wsq("molclr_gin_encoder_arena_bytes", L, N, D, dtype)
-        arena = torch.empty(max(arena_bytes // 4, 1), dtype=torch.float32, device=dev)
-        ws_bytes = _wsq("molclr_gin_encoder_workspace_bytes", L, N, D, dtype)
-        ws = _ws(ws_bytes, dev)
-        h = torch.empty(N, D, dtype=TORCH_DTYPE[dtype], device=dev)
-        gc = graph.cstruct()
-        _lib.call("molclr_gin_encoder_fwd", ctypes.addressof(enc), x_idx.data_ptr(),
-                  ctypes.addressof(gc), h.data_ptr(), arena.data_ptr(), arena_bytes,
-                  ws.data_ptr(), ws_bytes, _stream(x_idx))
-        if _TIMER is not None:
-            es = 2 if dtype == _lib.DTYPE_BF16 else 4
-            # the h3 forward's aggregation also stores its row maxima
-            rmb = _wsq("molclr_rowmax_bytes", N, D) if (enc.fp32_gemm & 2) else 0
-            for _ in range(L):
-                _TIMER.add("gine_aggregate_fwd",
-                           gine_aggregate_bytes(N, D, graph.num_edges, es) + rmb)
-                _TIMER.add("gemm_f32", 2 * 2.0 * N * D * (2 * D))
-        ctx.enc, ctx.graph, ctx.arena, ctx.arena_bytes = enc, graph, arena, arena_bytes
-        ctx.x_idx, ctx.params, ctx.training = x_idx, params, training
-        return h
-
-    @staticmethod
-    def backward(ctx, dh):
-        if not ctx.training:
-            raise NotImplementedError("molclr_amd: backward through eval-mode BatchNorm")
-        dtype = int(ctx.enc.dtype)
-        dh = _c(dh.to(TORCH_DTYPE[dtype]))
-        params = ctx.params
-        L = ctx.enc.num_layer
-        N, D = dh.shape
-        owned = all(getattr(p, "_molclr_fused_grad", False) and p.grad is not None
-                    for p in params)
-        if owned:  # FusedAdam: add straight into the flat gradient buffer
-            bufs = [p.grad for p in params]
-            ret = [None] * len(params)
-        else:
-            bufs = [torch.zeros_like(p) for p in params]
-            ret = bufs
-        gr = _lib.GinEncoderGrads()
-        gr.x_embedding1, gr.x_embedding2 = bufs[0].data_ptr(), bufs[1].data_ptr()
-        names = ("mlp0_weight", "mlp0_bias", "mlp2_weight", "mlp2_bias", "edge_embedding1",
-                 "edge_embedding2", "bn_weight", "bn_bias")
-        for l in range(L):
-            for j, nm in enumerate(names):
-                getattr(gr, nm)[l] = bufs[2 + GIN_PARAMS_PER_LAYER * l + j].data_ptr()
-        ws_bytes = _wsq("molclr_gin_encoder_workspace_bytes", L, N, D, dtype)
-        ws = _ws(ws_bytes, dh.device)
-        gc = ctx.graph.cstruct()
-        hook = _grad_events(gr, L, owned)
-        _lib.call("molclr_gin_encoder_bwd", ctypes.addressof(ctx.enc), ctypes.addressof(gr),
-                  ctx.x_idx.data_ptr(), ctypes.addressof(gc), dh.data_ptr(), ctx.arena.data_ptr(),
-                  ctx.arena_bytes, ws.data_ptr(), ws_bytes, _stream(dh))
-        if hook is not None:
-            hook.encoder_backward_enqueued()
-        if _TIMER is not None:
-            for _ in range(L):
-                _TIMER.add("gemm_f32", 4 * 2.0 * N * D * (2 * D))
-        ctx.arena = None
-        return (None, None, None, None, *ret)
-
-
-GCN_PARAMS_PER_LAYER = 6  # weight, bias, edge_emb1, edge_emb2, bn.W, bn.b
-
-
-class _GCNEncoder(torch.autograd.Function):
-    """GCN's node-embedding stack (gcn_molclr.py:140-151) through
-    molclr_gcn_encoder_fwd / _bwd (encoder.hip): the per-op path's kernels in
-    its order, one host call each way.
-    params: x_embedding1, x_embedding2, then per layer GCN_PARAMS_PER_LAYER."""
-
-    @staticmethod
-    def forward(ctx, x_idx, graph: DeviceGraph, bns, *params):
-        _check(x_idx, *params)
-        L = len(bns)
-        D = params[0].shape[1]
-        x_idx = _c(x_idx.to(torch.long))
-        N = graph.num_nodes
-        training = bool(bns[0].training)
-        enc = _lib.GcnEncoder()
-        enc.num_layer, enc.training, enc.dim = L, int(training), D
-        enc.n_atom, enc.n_chiral = params[0].shape[0], params[1].shape[0]
-        enc.momentum, enc.eps = float(bns[0].momentum), float(bns[0].eps)
-        enc.x_embedding1, enc.x_embedding2 = params[0].data_ptr(), params[1].data_ptr()
-        h3 = gcn_h3_ok(N, D)  # the form _GCNConv uses on these shapes
-        enc.fp32_gemm = int(h3)
-        enc.status = graph.status.data_ptr()
-        for l in range(L):
-            W, b, E1, E2, g, bb = params[2 + GCN_PARAMS_PER_LAYER * l:
-                                         2 + GCN_PARAMS_PER_LAYER * (l + 1)]
-            bn = bns[l]
-            enc.weight[l], enc.bias[l] = W.data_ptr(), b.data_ptr()
-            enc.edge_embedding1[l], enc.edge_embedding2[l] = E1.data_ptr(), E2.data_ptr()
-            enc.bn_weight[l], enc.bn_bias[l] = g.data_ptr(), bb.data_ptr()
-            enc.bn_running_mean[l] = bn.running_mean.data_ptr()
-            enc.bn_running_var[l] = bn.running_var.data_ptr()
-            nbt = bn.num_batches_tracked
-            enc.bn_num_batches_tracked[l] = nbt.data_ptr() if training and nbt is not None else None
-            # the planes (and cache entries) _GCNConv's gemm_w calls use
-            enc.weight_planes[l] = weight_planes(W, D, D, D, 1).data_ptr()
-            enc.weight_planes_t[l] = weight_planes(W, D, D, D, 0, "h3" if h3 else "x6").data_ptr()
-        dev = x_idx.device
-        arena_bytes = _wsq("molclr_gcn_encoder_arena_bytes", L, N, D)
-        arena = torch.empty(max(arena_bytes // 4, 1), dtype=torch.float32, device=dev)
-        ws_bytes = _wsq("molclr_gcn_encoder_workspace_bytes", L, N, D)
-        ws = _ws(ws_bytes, dev)
-        h = torch.empty(N, D, dtype=torch.float32, device=dev)
-        gc = graph.cstruct()
-        _lib.call("molclr_gcn_encoder_fwd", ctypes.addressof(enc), x_idx.data_ptr(),
-                  ctypes.addressof(gc), h.data_ptr(), arena.data_ptr(), arena_bytes,
-                  ws.data_ptr(), ws_bytes, _stream(x_idx))
-        if _TIMER is not None:
-            for _ in range(L):
-                _TIMER.add("gemm_f32", 2.0 * N * D * D)
-                # the GCN scatter-add moves the same compulsory bytes as GINE's
-                _TIMER.add("gcn_aggregate_fwd", gine_aggregate_bytes(N, D, graph.num_edges))
-        ctx.enc, ctx.graph, ctx.arena, ctx.arena_bytes = enc, graph, arena, arena_bytes
-        ctx.x_idx, ctx.params, ctx.training = x_idx, params, training
-        return h
-
-    @staticmethod
-    def backward(ctx, dh):
-        if not ctx.training:
-            raise NotImplementedError("molclr_amd: backward through eval-mode BatchNorm")
-        dh = _c(dh)
-        params = ctx.params
-        L = ctx.enc.num_layer
-        N, D = dh.shape
-        owned = all(getattr(p, "_molclr_fused_grad", False) and p.grad is not None
-                    for p in params)
-        if owned:  # FusedAdam: add straight into the flat gradient buffer
-            bufs = [p.grad for p in params]
-            ret = [None] * len(params)
-        else:
-            bufs = [torch.zeros_like(p) for p in params]
-            ret = bufs
-        gr = _lib.GcnEncoderGrads()
-        gr.x_embedding1, gr.x_embedding2 = bufs[0].data_ptr(), bufs[1].data_ptr()
-        names = ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight", "bn_bias")
-        for l in range(L):
-            for j, nm in enumerate(names):
-                getattr(gr, nm)[l] = bufs[2 + GCN_PARAMS_PER_LAYER * l + j].data_ptr()
-        ws_bytes = _wsq("molclr_gcn_encoder_workspace_bytes", L, N, D)
-        ws = _ws(ws_bytes, dh.device)
-        gc = ctx.graph.cstruct()
-        hook = _grad_events(gr, L, owned)
-        _lib.call("molclr_gcn_encoder_bwd", ctypes.addressof(ctx.enc), ctypes.addressof(gr),
-                  ctx.x_idx.data_ptr(), ctypes.addressof(gc), dh.data_ptr(), ctx.arena.data_ptr(),
-                  ctx.arena_bytes, ws.data_ptr(), ws_bytes, _stream(dh))
-        if hook is not None:
-            hook.encoder_backward_enqueued()
-        if _TIMER is not None:
-            for _ in range(L):
-                _TIMER.add("gemm_f32", 2 * 2.0 * N * D * D)
-        ctx.arena = None
-        return (None, None, None, *ret)
-
-
-def gcn_encoder(x_idx, graph, bns, params):
-    """GCN.encode through the encoder executor (see _GCNEncoder)."""
-    return _GCNEncoder.apply(x_idx, graph, bns, *params)
-
-
 DTYPES = {"fp32": _lib.DTYPE_F32, "bf16": _lib.DTYPE_BF16}
 TORCH_DTYPE = {_lib.DTYPE_F32: torch.float32, _lib.DTYPE_BF16: torch.bfloat16}
 
 
+@dataclasses.dataclass(frozen=True)
+class _EncoderKind:
+    """What tells the two encoder executors apart (see _Encoder)."""
+    struct: type  # the _lib mirror of struct <symbol>
+    grads: type  # ... and of struct <symbol>_grads
+    symbol: str  # C prefix of _fwd, _bwd, _arena_bytes, _workspace_bytes
+    layer_params: tuple  # per-layer parameter fields, in the order of params
+    sized_by_dtype: bool  # the size queries take the dtype after (L, N, D)
+    fill: object  # (enc, layers, N, D, dtype): the GEMM form and the weight planes
+    account: object  # (enc, graph, N, D, dtype, backward): one layer's KernelTimer work
+
+
+def _gin_fill(enc, layers, N, D, dtype):
+    enc.dtype = dtype
+    # fp32: the GEMM form ops._MLP would use on these shapes (identical kernels)
+    h3 = dtype == _lib.DTYPE_F32 and h3_ok(N, D)
+    kind = "h3" if h3 and H3_FORWARD else "x6"
+    kind_t = "h3" if h3 else "x6"
+    enc.fp32_gemm = (1 | (2 if H3_FORWARD else 0)) if h3 else 0
+    for l, (W0, _, W2, *_) in enumerate(layers):
+        twoD = W0.shape[0]
+        # the same planes (and cache entries) ops.linear_fwd / linear_bwd use
+        enc.mlp0_planes[l] = weight_planes(W0, twoD, D, D, 0, kind).data_ptr()
+        enc.mlp0_planes_t[l] = weight_planes(W0, D, twoD, D, 1, kind_t).data_ptr()
+        enc.mlp2_planes[l] = weight_planes(W2, D, twoD, twoD, 0, kind).data_ptr()
+        enc.mlp2_planes_t[l] = weight_planes(W2, twoD, D, twoD, 1, kind_t).data_ptr()
+
+
+def _gin_account(enc, graph, N, D, dtype, backward):
+    if backward:
+        _TIMER.add("gemm_f32", 4 * 2.0 * N * D * (2 * D))
+        return
+    es = 2 if dtype == _lib.DTYPE_BF16 else 4
+    # the h3 forward's aggregation also stores its row maxima
+    rmb = _wsq("molclr_rowmax_bytes", N, D) if (enc.fp32_gemm & 2) else 0
+    _TIMER.add("gine_aggregate_fwd", gine_aggregate_bytes(N, D, graph.num_edges, es) + rmb)
+    _TIMER.add("gemm_f32", 2 * 2.0 * N * D * (2 * D))
+
+
+def _gcn_fill(enc, layers, N, D, dtype):
+    h3 = gcn_h3_ok(N, D)  # the form _GCNConv uses on these shapes
+    enc.fp32_gemm = int(h3)
+    for l, (W, *_) in enumerate(layers):
+        # the planes (and cache entries) _GCNConv's gemm_w calls use
+        enc.weight_planes[l] = weight_planes(W, D, D, D, 1).data_ptr()
+        enc.weight_planes_t[l] = weight_planes(W, D, D, D, 0, "h3" if h3 else "x6").data_ptr()
+
+
+def _gcn_account(enc, graph, N, D, dtype, backward):
+    if backward:
+        _TIMER.add("gemm_f32", 2 * 2.0 * N * D * D)
+        return
+    _TIMER.add("gemm_f32", 2.0 * N * D * D)
+    # the GCN scatter-add moves the same compulsory bytes as GINE's
+    _TIMER.add("gcn_aggregate_fwd", gine_aggregate_bytes(N, D, graph.num_edges))
+
+
+_GIN = _EncoderKind(_lib.GinEncoder, _lib.GinEncoderGrads, "molclr_gin_encoder",
+                    _lib.GIN_LAYER_PARAMS, True, _gin_fill, _gin_account)
+_GCN = _EncoderKind(_lib.GcnEncoder, _lib.GcnEncoderGrads, "molclr_gcn_encoder",
+                    _lib.GCN_LAYER_PARAMS, False, _gcn_fill, _gcn_account)
+GIN_PARAMS_PER_LAYER = len(_GIN.layer_params)
+GCN_PARAMS_PER_LAYER = len(_GCN.layer_params)
+
+
+class _Encoder(torch.autograd.Function):
+    """A whole node-embedding stack (ginet_molclr.py:98-111,
+    gcn_molclr.py:140-151) through <kind.symbol>_fwd / _bwd (encoder.hip): the
+    same kernels as the per-op path in the same order, one host call each way.
+    params: x_embedding1, x_embedding2, then per layer kind.layer_params."""
+
+    @staticmethod
+    def forward(ctx, kind: _EncoderKind, x_idx, graph: DeviceGraph, bns, dtype, *params):
+        _check(x_idx, *params)
+        L = len(bns)
+        D = params[0].shape[1]
+        x_idx = _c(x_idx.to(torch.long))
+        N = graph.num_nodes
+        training = bool(bns[0].training)
+        enc = kind.struct()
+        enc.num_layer, enc.training, enc.dim = L, int(training), D
+        enc.status = graph.status.data_ptr()  # out-of-vocabulary atoms: MOLCLR_STATUS_ATOM_RANGE
+        enc.n_atom, enc.n_chiral = params[0].shape[0], params[1].shape[0]
+        enc.momentum, enc.eps = float(bns[0].momentum), float(bns[0].eps)
+        enc.x_embedding1, enc.x_embedding2 = params[0].data_ptr(), params[1].data_ptr()
+        n = len(kind.layer_params)
+        layers = [params[2 + n * l: 2 + n * (l + 1)] for l in range(L)]
+        fields = [getattr(enc, nm) for nm in kind.layer_params]
+        for l, (layer, bn) in enumerate(zip(layers, bns)):
+            for field, t in zip(fields, layer):
+                field[l] = t.data_ptr()
+            enc.bn_running_mean[l] = bn.running_mean.data_ptr()
+            enc.bn_running_var[l] = bn.running_var.data_ptr()
+            nbt = bn.num_batches_tracked
+            enc.bn_num_batches_tracked[l] = nbt.data_ptr() if training and nbt is not None else None
+        kind.fill(enc, layers, N, D, dtype)
+        dev = x_idx.device
+        sizes = (L, N, D, dtype) if kind.sized_by_dtype else (L, N, D)
+        arena_bytes = _wsq(kind.symbol + "_arena_bytes", *sizes)
+        arena = torch.empty(max(arena_bytes // 4, 1), dtype=torch.float32, device=dev)
+        ws_bytes = _wsq(kind.symbol + "_workspace_bytes", *sizes)
+        ws = _ws(ws_bytes, dev)
+        h = torch.empty(N, D, dtype=TORCH_DTYPE[dtype], device=dev)
+        gc = graph.cstruct()
+        _lib.call(kind.symbol + "_fwd", ctypes.addressof(enc), x_idx.data_ptr(),
+                  ctypes.addressof(gc), h.data_ptr(), arena.data_ptr(), arena_bytes,
+                  ws.data_ptr(), ws_bytes, _stream(x_idx))
+        if _TIMER is not None:
+            for _ in range(L):
+                kind.account(enc, graph, N, D, dtype, False)
+        ctx.kind, ctx.enc, ctx.dtype, ctx.sizes = kind, enc, dtype, sizes
+        ctx.graph, ctx.arena, ctx.arena_bytes = graph, arena, arena_bytes
+        ctx.x_idx, ctx.params, ctx.training = x_idx, params, training
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        if not ctx.training:
+            raise NotImplementedError("molclr_amd: backward through eval-mode BatchNorm")
+        kind = ctx.kind
+        dh = _c(dh.to(TORCH_DTYPE[ctx.dtype]))
+        params = ctx.params
+        L = ctx.enc.num_layer
+        N, D = dh.shape
+        owned = all(getattr(p, "_molclr_fused_grad", False) and p.grad is not None
+                    for p in params)
+        if owned:  # FusedAdam: add straight into the flat gradient buffer
+            bufs = [p.grad for p in params]
+            ret = [None] * len(params)
+        else:
+            bufs = [torch.zeros_like(p) for p in params]
+            ret = bufs
+        gr = kind.grads()
+        gr.x_embedding1, gr.x_embedding2 = bufs[0].data_ptr(), bufs[1].data_ptr()
+        n = len(kind.layer_params)
+        for j, nm in enumerate(kind.layer_params):
+            field = getattr(gr, nm)
+            for l in range(L):
+                field[l] = bufs[2 + n * l + j].data_ptr()
+        ws_bytes = _wsq(kind.symbol + "_workspace_bytes", *ctx.sizes)
+        ws = _ws(ws_bytes, dh.device)
+        gc = ctx.graph.cstruct()
+        hook = _grad_events(gr, L, owned)
+        _lib.call(kind.symbol + "_bwd", ctypes.addressof(ctx.enc), ctypes.addressof(gr),
+                  ctx.x_idx.data_ptr(), ctypes.addressof(gc), dh.data_ptr(), ctx.arena.data_ptr(),
+                  ctx.arena_bytes, ws.data_ptr(), ws_bytes, _stream(dh))
+        if hook is not None:
+            hook.encoder_backward_enqueued()
+        if _TIMER is not None:
+            for _ in range(L):
+                kind.account(ctx.enc, ctx.graph, N, D, ctx.dtype, True)
+        ctx.arena = None
+        return (None, None, None, None, None, *ret)
+
+
+def gcn_encoder(x_idx, graph, bns, params):
+    """GCN.encode through the encoder executor (see _Encoder)."""
+    return _Encoder.apply(_GCN, x_idx, graph, bns, _lib.DTYPE_F32, *params)
+
+
 def gin_encoder(x_idx, graph, bns, params, precision: str = "fp32"):
-    """GINet.encode through the encoder executor (see _GINEncoder); precision
+    """GINet.encode through the encoder executor (see _Encoder); precision
     "bf16" runs the c5 configuration's bf16 storage / bf16 MFMA path and
     returns bf16 node embeddings."""
-    return _GINEncoder.apply(x_idx, graph, bns, DTYPES[precision], *params)
+    return _Encoder.apply(_GIN, x_idx, graph, bns, DTYPES[precision], *params)
 
 
 # public functional API -------------------------------------------------------

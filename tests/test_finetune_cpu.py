@@ -60,9 +60,9 @@ def test_seeded_initialisation_follows_creation_order():
 
 @pytest.mark.parametrize("kind", ("gin", "gcn"))
 def test_subclass_sets_what_the_parent_init_sets(kind):
-    """The fine-tuning classes restate the parent's __init__ (they must not
-    create out_lin): every attribute and submodule the parent sets, except
-    out_lin, is there with the same value."""
+    """The fine-tuning classes skip the parent's __init__ (they must not
+    create out_lin) and share its Encoder._init_encoder: every attribute and
+    submodule the parent sets, except out_lin, is there with the same value."""
     if kind == "gin":
         parent = ginet_molclr.GINet(2, 12, 10, 0.2, 'add')
         child = ginet_finetune.GINet('regression', 2, 12, 10, 0.2, 'add')
