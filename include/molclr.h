@@ -805,6 +805,15 @@ int molclr_step_tail(int32_t* step, const float* loss_src, float* loss_dst,
  *   mlp2_planes_t : B(k,n) = W2[k][n], N = 2D, K = D   (ldb = 2D, b_kmajor 1)
  * BatchNorm: training = batch statistics + running-stat update (momentum,
  * num_batches_tracked may be NULL); eval = running statistics (no backward).
+ * Dropout (training and drop_ratio > 0; the reference's F.dropout after every
+ * BatchNorm, after the ReLU where there is one): a counter-based mask (see
+ * molclr_dropout_mask) recomputed wherever a layer's output is used -- the
+ * apply that stores it, the next layer's gather, the BatchNorm backward -- so
+ * it costs no buffer and one extra launch per forward: the forward's first
+ * launch is molclr_dropout_next_key(drop_state, <the arena's key slot>), and
+ * every kernel of that forward and of its backward reads the key from the
+ * arena.  A backward therefore sees its own forward's masks however many
+ * forwards ran in between, and a replayed HIP graph draws fresh masks.
  * ------------------------------------------------------------------------ */
 typedef struct molclr_gin_encoder {
   int32_t num_layer;  /* 1 .. MOLCLR_MAX_LAYERS */
@@ -849,6 +858,11 @@ typedef struct molclr_gin_encoder {
   int32_t fp32_gemm;
   /* nullable: receives MOLCLR_STATUS_ATOM_RANGE (molclr_atom_embed_fwd) */
   int32_t* status;
+  /* dropout after every BatchNorm: 0 <= drop_ratio < 1; drop_state: device
+   * [seed, call counter] (NULL allowed unless training with drop_ratio > 0).
+   * Both are ignored in eval mode. */
+  double drop_ratio;
+  int64_t* drop_state;
 } molclr_gin_encoder;
 
 /* Gradient buffers, same shapes as the parameters; NULL = not needed. */
@@ -941,6 +955,8 @@ typedef struct molclr_gcn_encoder {
    * images, dim <= 1024). */
   int32_t fp32_gemm;
   int32_t* status; /* nullable: MOLCLR_STATUS_ATOM_RANGE, as molclr_gin_encoder */
+  double drop_ratio;   /* as molclr_gin_encoder */
+  int64_t* drop_state; /* as molclr_gin_encoder */
 } molclr_gcn_encoder;
 
 typedef struct molclr_gcn_encoder_grads {
@@ -966,6 +982,24 @@ int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* enc, const molclr_gcn_encod
                            const int64_t* x, const molclr_device_graph* graph,
                            const float* dh_out, const void* arena, size_t arena_bytes,
                            void* workspace, size_t workspace_bytes, molclr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The executors' dropout stream.  Philox4x32-10 (multipliers 0xD2511F53 /
+ * 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), one call per float4
+ * column unit: counter (row, column / 4, layer, call_lo), key (seed_lo,
+ * seed_hi ^ call_hi); output word j decides column 4 (column / 4) + j.  An
+ * element is kept iff word >= (uint32_t)(p * 2^32); kept elements are
+ * multiplied by 1 / (1 - p), dropped ones are exactly 0.  `row` is the row of
+ * the graph the executor sees (both views' rows in a paired pass).
+ * ------------------------------------------------------------------------ */
+/* key_out[0..1] = state[0..1] = (seed, call counter), then counter += 1; one
+ * one-thread launch, all on the device. */
+int molclr_dropout_next_key(int64_t* state, int64_t* key_out, molclr_stream_t stream);
+/* keep [N, D] (D a multiple of 4): 1 where layer `layer`'s dropout with
+ * probability p keeps the element under `key` (device [seed, call]), else 0;
+ * computed by the device function the executors' kernels use. */
+int molclr_dropout_mask(const int64_t* key, int layer, double p, uint8_t* keep, int64_t N,
+                        int64_t D, molclr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * bf16 storage (BASELINE config c5: GIN 5 x 512, bf16, batch 1024 / GPU).

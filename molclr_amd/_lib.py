@@ -156,6 +156,8 @@ SIGNATURES = {
     "molclr_gcn_encoder_workspace_bytes": (c_size_t, [c_int, _I64, _I64]),
     "molclr_gcn_encoder_fwd": (c_int, [_P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "molclr_gcn_encoder_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "molclr_dropout_next_key": (c_int, [_P, _P, _P]),
+    "molclr_dropout_mask": (c_int, [_P, c_int, c_double, _P, _I64, _I64, _P]),
     "molclr_aug_views_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
     "molclr_aug_views_plan": (c_int, [_P, _P, _P, _I64, _I64, _P, _I64, ctypes.c_uint64, c_int,
                                       c_int, _I64, _I64, _P, _P, _P, _P, c_size_t, _P]),
@@ -233,7 +235,8 @@ def _encoder_fields(layer_params, planes, tail):
             ("eps", c_double), ("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
         (f, _L16) for f in layer_params + ("bn_running_mean", "bn_running_var",
                                            "bn_num_batches_tracked") + planes] + tail + [
-        ("fp32_gemm", ctypes.c_int32), ("status", c_void_p)]
+        ("fp32_gemm", ctypes.c_int32), ("status", c_void_p), ("drop_ratio", c_double),
+        ("drop_state", c_void_p)]
 
 
 def _encoder_grads_fields(layer_params):

@@ -342,19 +342,28 @@ __device__ __forceinline__ float4 gine_msg(const float4* __restrict__ x, const f
 // column for its DESTINATION row's segment: in a batched graph every in-edge
 // comes from the same graph, hence the same segment.  A padding row of a
 // device-sized plan reads zero, the y the apply writes there.
+// DR = DropArgs: dropout follows the BatchNorm (+ReLU), as in k_bn_apply: the
+// mask of SOURCE row j, column unit c (dropout.h), recomputed by every reader
+// of the row, before the bf16 rounding.
 struct NoSrcArgs {};
-struct BnSrcArgs {
+template <typename DR>
+struct BnSrcArgsT {
   const float4* scale;  // [nseg][D / 4]
   const float4* shift;
   int relu;
   Segs sg;
+  DR drop;
 };
+typedef BnSrcArgsT<NoDrop> BnSrcArgs;
 
-template <typename St>
-__device__ __forceinline__ float4 bn_src_unit(float4 v, float4 sc, float4 sh, bool relu) {
+// row j, float4 column unit c4 of the BatchNorm input
+template <typename St, typename DR>
+__device__ __forceinline__ float4 bn_src_unit(float4 v, float4 sc, float4 sh, bool relu,
+                                              const Drop<DR>& drop, int64_t j, int c4) {
   float4 o = make_float4(bn_apply1(v.x, sc.x, sh.x), bn_apply1(v.y, sc.y, sh.y),
                          bn_apply1(v.z, sc.z, sh.z), bn_apply1(v.w, sc.w, sh.w));
   if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+  if constexpr (DR::kOn) o = drop(o, j, c4);
   if constexpr (St::kBytes == 2) {  // as StBF16::st stores y and ::ld reads it
     const uint32_t lo = f32x2_to_bf16x2(o.x, o.y), hi = f32x2_to_bf16x2(o.z, o.w);
     o = make_float4(bf16_to_f32(lo & 0xFFFFu), bf16_to_f32(lo >> 16), bf16_to_f32(hi & 0xFFFFu),
@@ -363,30 +372,34 @@ __device__ __forceinline__ float4 bn_src_unit(float4 v, float4 sc, float4 sh, bo
   return o;
 }
 
-// the source of destination row i, float4 column c: X(x, unit) is one column unit
+// the source of destination row i, float4 column c: X(x, unit, j) is one column
+// unit, of row j
 template <typename St, typename SA>
 struct AggSrc {
   __device__ __forceinline__ AggSrc(const SA&, int64_t, int, int) {}
-  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x,
-                                               int64_t unit) const {
+  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x, int64_t unit,
+                                               int64_t) const {
     return St::ld(x, unit);
   }
 };
-template <typename St>
-struct AggSrc<St, BnSrcArgs> {
+template <typename St, typename DR>
+struct AggSrc<St, BnSrcArgsT<DR>> {
   float4 sc, sh;
   bool relu, pad;
-  __device__ __forceinline__ AggSrc(const BnSrcArgs& a, int64_t i, int c, int d4) {
+  int c;
+  Drop<DR> drop;
+  __device__ __forceinline__ AggSrc(const BnSrcArgsT<DR>& a, int64_t i, int c_, int d4)
+      : c(c_), drop(a.drop) {
     const int s = seg_of_row(a.sg, i);
     pad = s < 0;
     relu = a.relu != 0;
     sc = pad ? f4zero() : a.scale[s * d4 + c];
     sh = pad ? f4zero() : a.shift[s * d4 + c];
   }
-  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x,
-                                               int64_t unit) const {
+  __device__ __forceinline__ float4 operator()(const typename St::T* __restrict__ x, int64_t unit,
+                                               int64_t j) const {
     if (pad) return f4zero();
-    return bn_src_unit<St>(St::ld(x, unit), sc, sh, relu);
+    return bn_src_unit<St, DR>(St::ld(x, unit), sc, sh, relu, drop, j, c);
   }
 };
 
@@ -403,12 +416,12 @@ __device__ __forceinline__ float4 gine_agg_elem(
     const uint4* __restrict__ nbr, const float4* __restrict__ Ec, typename St::T* __restrict__ out,
     int64_t t, int64_t i, int c, int d4, const SA& sa) {
   const AggSrc<St, SA> src(sa, i, c, d4);
-  auto X = [&](int64_t idx) { return src(x, idx); };
+  auto X = [&](int64_t j) { return src(x, j * d4 + c, j); };
   auto msg = [&](uint32_t w) {
-    return f4add(X((int64_t)nbr_node(w) * d4 + c), Ec[nbr_ecomb(w) * d4 + c]);
+    return f4add(X((int64_t)nbr_node(w)), Ec[nbr_ecomb(w) * d4 + c]);
   };
   const uint4 s = nbr[i];
-  const float4 self = X(t);
+  const float4 self = src(x, t, i);
   const float4 es = Ec[MOLCLR_SELF_LOOP_ECOMB * d4 + c];
   const uint32_t deg = nbr_degree(s.x);
   float4 acc = f4zero();
@@ -423,7 +436,7 @@ __device__ __forceinline__ float4 gine_agg_elem(
     if (deg > 3) acc = f4add(acc, m3);
   } else {
     for (int32_t k = rowptr[i], e = rowptr[i + 1]; k < e; ++k)
-      acc = f4add(acc, f4add(X((int64_t)col[k] * d4 + c), Ec[MOLCLR_ECOMB(ecode[k]) * d4 + c]));
+      acc = f4add(acc, f4add(X((int64_t)col[k]), Ec[MOLCLR_ECOMB(ecode[k]) * d4 + c]));
   }
   acc = f4add(acc, f4add(self, es));
   if constexpr (NT) {  // fp32 only
@@ -727,15 +740,19 @@ __device__ __forceinline__ F8 ec8(const float4* __restrict__ Ec, int comb, int d
 template <typename SA>
 struct AggSrc8 {
   __device__ __forceinline__ AggSrc8(const SA&, int64_t, int, int) {}
-  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit) const {
+  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit,
+                                           int64_t) const {
     return ld8(x, unit);
   }
 };
-template <>
-struct AggSrc8<BnSrcArgs> {
+template <typename DR>
+struct AggSrc8<BnSrcArgsT<DR>> {
   float4 sc[2], sh[2];
   bool relu, pad;
-  __device__ __forceinline__ AggSrc8(const BnSrcArgs& a, int64_t i, int c, int d8) {
+  int c;
+  Drop<DR> drop;
+  __device__ __forceinline__ AggSrc8(const BnSrcArgsT<DR>& a, int64_t i, int c_, int d8)
+      : c(c_), drop(a.drop) {
     const int s = seg_of_row(a.sg, i);
     pad = s < 0;
     relu = a.relu != 0;
@@ -745,10 +762,12 @@ struct AggSrc8<BnSrcArgs> {
       sh[j] = pad ? f4zero() : a.shift[(s * d8 + c) * 2 + j];
     }
   }
-  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit) const {
+  __device__ __forceinline__ F8 operator()(const uint16_t* __restrict__ x, int64_t unit,
+                                           int64_t j) const {
     if (pad) return {f4zero(), f4zero()};
     const F8 v = ld8(x, unit);
-    return {bn_src_unit<StBF16>(v.a, sc[0], sh[0], relu), bn_src_unit<StBF16>(v.b, sc[1], sh[1], relu)};
+    return {bn_src_unit<StBF16, DR>(v.a, sc[0], sh[0], relu, drop, j, 2 * c),
+            bn_src_unit<StBF16, DR>(v.b, sc[1], sh[1], relu, drop, j, 2 * c + 1)};
   }
 };
 
@@ -764,10 +783,10 @@ __global__ __launch_bounds__(kT) void k_gine_agg_fwd_b8(
   const int c = (int)(t - i * d8);
   const AggSrc8<SA> src(sa, i, c, d8);
   auto msg = [&](uint32_t w) {
-    return f8add(src(x, (int64_t)nbr_node(w) * d8 + c), ec8(Ec, nbr_ecomb(w), d8, c));
+    return f8add(src(x, (int64_t)nbr_node(w) * d8 + c, nbr_node(w)), ec8(Ec, nbr_ecomb(w), d8, c));
   };
   const uint4 s = nbr[i];
-  const F8 self = src(x, t);
+  const F8 self = src(x, t, i);
   const F8 es = ec8(Ec, MOLCLR_SELF_LOOP_ECOMB, d8, c);
   const uint32_t deg = nbr_degree(s.x);
   F8 acc = {f4zero(), f4zero()};
@@ -782,7 +801,8 @@ __global__ __launch_bounds__(kT) void k_gine_agg_fwd_b8(
     if (deg > 3) acc = f8add(acc, m3);
   } else {
     for (int32_t k = rowptr[i], e = rowptr[i + 1]; k < e; ++k)
-      acc = f8add(acc, f8add(src(x, (int64_t)col[k] * d8 + c), ec8(Ec, MOLCLR_ECOMB(ecode[k]), d8, c)));
+      acc = f8add(acc, f8add(src(x, (int64_t)col[k] * d8 + c, col[k]),
+                             ec8(Ec, MOLCLR_ECOMB(ecode[k]), d8, c)));
   }
   st8(out, t, f8add(acc, f8add(self, es)));
 }
@@ -1162,9 +1182,10 @@ MOLCLR_API int molclr_gine_aggregate_fwd_bf16(const uint16_t* x, const int32_t* 
 }
 
 // BatchNorm source: the segments of the rows, host- or device-sized
+template <typename DR>
 static int agg_bn_args(const char* who, const float* coeffs, int relu, int nseg,
                        const int64_t* seg_rows, const int64_t* seg_rows_dev, int64_t N, int64_t D,
-                       BnSrcArgs& a) {
+                       BnSrcArgsT<DR>& a) {
   MOLCLR_REQUIRE(coeffs && ((uintptr_t)coeffs & 15) == 0, "%s: coeffs null or not 16-byte aligned", who);
   MOLCLR_REQUIRE(nseg >= 1 && nseg <= MOLCLR_MAX_SEGMENTS && (seg_rows || seg_rows_dev),
                  "%s: %d segments (1..%d)", who, nseg, MOLCLR_MAX_SEGMENTS);
@@ -1185,42 +1206,84 @@ static int agg_bn_args(const char* who, const float* coeffs, int relu, int nseg,
   return MOLCLR_OK;
 }
 
-MOLCLR_API int molclr_gine_aggregate_bn_fwd(const float* z, const float* coeffs, int relu, int nseg,
-                                            const int64_t* seg_rows, const int64_t* seg_rows_dev,
-                                            const int32_t* rowptr, const int32_t* col,
-                                            const uint8_t* ecode, const uint32_t* nbr,
-                                            const float* Ec, float* out, int64_t N, int64_t D,
-                                            float* rowparts, float* slot, molclr_stream_t stream) {
+// molclr_gine_aggregate_bn_fwd with or without dropout (DR)
+template <typename DR>
+static int agg_bn_fwd_f32(const float* z, const float* coeffs, int relu, int nseg,
+                          const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                          const int32_t* rowptr, const int32_t* col, const uint8_t* ecode,
+                          const uint32_t* nbr, const float* Ec, float* out, int64_t N, int64_t D,
+                          float* rowparts, float* slot, const DR& drop, hipStream_t s) {
   MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bn_fwd: dim %lld must be a multiple of 4",
                  (long long)D);
   MOLCLR_REQUIRE(N < (1ll << 31), "gine_aggregate_bn_fwd: too many rows");
   MOLCLR_REQUIRE(rowparts || !slot, "gine_aggregate_bn_fwd: a slot needs rowparts");
   if (N == 0) return MOLCLR_OK;
   MOLCLR_REQUIRE(z && rowptr && nbr && Ec && out, "gine_aggregate_bn_fwd: null pointer");
-  BnSrcArgs a;
+  typedef BnSrcArgsT<DR> SA;
+  SA a;
+  a.drop = drop;
   MOLCLR_TRY_RC(agg_bn_args("gine_aggregate_bn_fwd", coeffs, relu, nseg, seg_rows, seg_rows_dev, N,
                             D, a));
   const int d4 = (int)(D / 4);
   const dim3 grid(molclr::ceil_div(N * d4, kT));
-  hipStream_t s = molclr::as_stream(stream);
   const uint4* nb = (const uint4*)nbr;
   const float4* ec = (const float4*)Ec;
   if (rowparts) {
     const int np = (int)molclr_rowmax_layout(D);
     molclr::launch_timed(molclr::kTimeGineAgg,
-                         agg_nt() ? k_gine_agg_fwd<StF32, true, true, BnSrcArgs>
-                                  : k_gine_agg_fwd<StF32, true, false, BnSrcArgs>,
+                         agg_nt() ? k_gine_agg_fwd<StF32, true, true, SA>
+                                  : k_gine_agg_fwd<StF32, true, false, SA>,
                          grid, dim3(kT), 0, s, z, rowptr, col, ecode, nb, ec, out, N, d4, rowparts,
                          np, slot, a);
   } else {
     molclr::launch_timed(molclr::kTimeGineAgg,
-                         agg_nt() ? k_gine_agg_fwd<StF32, false, true, BnSrcArgs>
-                                  : k_gine_agg_fwd<StF32, false, false, BnSrcArgs>,
+                         agg_nt() ? k_gine_agg_fwd<StF32, false, true, SA>
+                                  : k_gine_agg_fwd<StF32, false, false, SA>,
                          grid, dim3(kT), 0, s, z, rowptr, col, ecode, nb, ec, out, N, d4,
                          (float*)nullptr, 0, (float*)nullptr, a);
   }
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
+}
+
+template <typename DR>
+static int agg_bn_fwd_bf16(const uint16_t* z, const float* coeffs, int relu, int nseg,
+                           const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                           const int32_t* rowptr, const int32_t* col, const uint8_t* ecode,
+                           const uint32_t* nbr, const float* Ec, uint16_t* out, int64_t N,
+                           int64_t D, const DR& drop, hipStream_t s) {
+  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bn_fwd_bf16: dim must be a multiple of 4");
+  if (N == 0) return MOLCLR_OK;
+  MOLCLR_REQUIRE(z && rowptr && nbr && Ec && out, "gine_aggregate_bn_fwd_bf16: null pointer");
+  typedef BnSrcArgsT<DR> SA;
+  SA a;
+  a.drop = drop;
+  MOLCLR_TRY_RC(agg_bn_args("gine_aggregate_bn_fwd_bf16", coeffs, relu, nseg, seg_rows,
+                            seg_rows_dev, N, D, a));
+  if (D % 8 == 0) {
+    const int d8 = (int)(D / 8);
+    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd_b8<SA>,
+                         dim3(molclr::ceil_div(N * d8, kT)), dim3(kT), 0, s, z, rowptr, col, ecode,
+                         (const uint4*)nbr, (const float4*)Ec, out, N, d8, a);
+  } else {
+    const int d4 = (int)(D / 4);
+    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd<StBF16, false, false, SA>,
+                         dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, s, z, rowptr, col, ecode,
+                         (const uint4*)nbr, (const float4*)Ec, out, N, d4, (float*)nullptr, 0,
+                         (float*)nullptr, a);
+  }
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+MOLCLR_API int molclr_gine_aggregate_bn_fwd(const float* z, const float* coeffs, int relu, int nseg,
+                                            const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                            const int32_t* rowptr, const int32_t* col,
+                                            const uint8_t* ecode, const uint32_t* nbr,
+                                            const float* Ec, float* out, int64_t N, int64_t D,
+                                            float* rowparts, float* slot, molclr_stream_t stream) {
+  return agg_bn_fwd_f32(z, coeffs, relu, nseg, seg_rows, seg_rows_dev, rowptr, col, ecode, nbr, Ec,
+                        out, N, D, rowparts, slot, NoDrop{}, molclr::as_stream(stream));
 }
 
 MOLCLR_API int molclr_gine_aggregate_bn_fwd_bf16(const uint16_t* z, const float* coeffs, int relu,
@@ -1230,26 +1293,23 @@ MOLCLR_API int molclr_gine_aggregate_bn_fwd_bf16(const uint16_t* z, const float*
                                                  const uint8_t* ecode, const uint32_t* nbr,
                                                  const float* Ec, uint16_t* out, int64_t N,
                                                  int64_t D, molclr_stream_t stream) {
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bn_fwd_bf16: dim must be a multiple of 4");
-  if (N == 0) return MOLCLR_OK;
-  MOLCLR_REQUIRE(z && rowptr && nbr && Ec && out, "gine_aggregate_bn_fwd_bf16: null pointer");
-  BnSrcArgs a;
-  MOLCLR_TRY_RC(agg_bn_args("gine_aggregate_bn_fwd_bf16", coeffs, relu, nseg, seg_rows,
-                            seg_rows_dev, N, D, a));
-  if (D % 8 == 0) {
-    const int d8 = (int)(D / 8);
-    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd_b8<BnSrcArgs>,
-                         dim3(molclr::ceil_div(N * d8, kT)), dim3(kT), 0, molclr::as_stream(stream),
-                         z, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d8, a);
-  } else {
-    const int d4 = (int)(D / 4);
-    molclr::launch_timed(molclr::kTimeGineAgg, k_gine_agg_fwd<StBF16, false, false, BnSrcArgs>,
-                         dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
-                         z, rowptr, col, ecode, (const uint4*)nbr, (const float4*)Ec, out, N, d4,
-                         (float*)nullptr, 0, (float*)nullptr, a);
-  }
-  MOLCLR_LAUNCHED();
-  return MOLCLR_OK;
+  return agg_bn_fwd_bf16(z, coeffs, relu, nseg, seg_rows, seg_rows_dev, rowptr, col, ecode, nbr,
+                         Ec, out, N, D, NoDrop{}, molclr::as_stream(stream));
+}
+
+int molclr::gine_aggregate_bn_fwd_drop(const void* z, const float* coeffs, int relu, int nseg,
+                                       const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                       const int32_t* rowptr, const int32_t* col,
+                                       const uint8_t* ecode, const uint32_t* nbr, const float* Ec,
+                                       void* out, int64_t N, int64_t D, int dtype, float* rowparts,
+                                       float* slot, const DropArgs& drop, hipStream_t s) {
+  if (dtype == MOLCLR_DTYPE_F32)
+    return agg_bn_fwd_f32((const float*)z, coeffs, relu, nseg, seg_rows, seg_rows_dev, rowptr, col,
+                          ecode, nbr, Ec, (float*)out, N, D, rowparts, slot, drop, s);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16 && !rowparts && !slot,
+                 "gine_aggregate_bn_fwd_drop: dtype %d (row maxima are fp32 only)", dtype);
+  return agg_bn_fwd_bf16((const uint16_t*)z, coeffs, relu, nseg, seg_rows, seg_rows_dev, rowptr,
+                         col, ecode, nbr, Ec, (uint16_t*)out, N, D, drop, s);
 }
 
 MOLCLR_API int molclr_gine_aggregate_bwd_bf16(const uint16_t* g, const int32_t* rowptr_t,

@@ -9,6 +9,7 @@
 #include <stddef.h>
 
 #include "../../include/molclr.h"
+#include "dropout.h"
 
 #define MOLCLR_API extern "C" __attribute__((visibility("default")))
 
@@ -179,6 +180,37 @@ inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipStream
 
 // norm.hip: BatchNorm workspace for any split of `rows` into segments
 size_t molclr_batchnorm_ws_bound(int64_t rows, int64_t D);
+
+// The encoder executors' kernels with dropout after the BatchNorm (dropout.h;
+// the public entry points keep their signatures and run without it).
+// Segments: host-sized (seg_rows) or device-sized (seg_rows_dev, rows_cap).
+namespace molclr {
+// norm.hip: molclr_batchnorm_seg_fwd / _fwd_dev, the stored y dropped
+int batchnorm_seg_fwd_drop(const void* z, const float* gamma, const float* beta,
+                           float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                           void* y, float* save_mean, float* save_invstd, int nseg,
+                           const int64_t* seg_rows, const int64_t* seg_rows_dev, int64_t rows_cap,
+                           int64_t D, int dtype, double momentum, double eps, int training,
+                           int relu, const DropArgs& drop, void* workspace, size_t workspace_bytes,
+                           hipStream_t s);
+// norm.hip: molclr_batchnorm_seg_bwd / _bwd_max / _bwd_dev, dy the gradient
+// behind the dropout
+int batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* gamma, const float* beta,
+                           const float* save_mean, const float* save_invstd, void* dz,
+                           float* dgamma, float* dbeta, int nseg, const int64_t* seg_rows,
+                           const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D, int dtype,
+                           int relu, int accumulate, float* rowmax, float* slot,
+                           const DropArgs& drop, void* workspace, size_t workspace_bytes,
+                           hipStream_t s);
+// aggregate.hip: molclr_gine_aggregate_bn_fwd / _bf16, every source element
+// dropped after the BatchNorm (+ReLU), before the bf16 rounding
+int gine_aggregate_bn_fwd_drop(const void* z, const float* coeffs, int relu, int nseg,
+                               const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                               const int32_t* rowptr, const int32_t* col, const uint8_t* ecode,
+                               const uint32_t* nbr, const float* Ec, void* out, int64_t N,
+                               int64_t D, int dtype, float* rowparts, float* slot,
+                               const DropArgs& drop, hipStream_t s);
+}  // namespace molclr
 
 #define MOLCLR_REQUIRE(cond, ...)        \
   do {                                   \

@@ -15,6 +15,12 @@
 // gathers (molclr_gine_aggregate_bn_fwd; the backward reads z, never h).  The
 // last layer's apply writes h_out.  MOLCLR_AGG_BN=0 (an A/B switch) keeps the
 // stored h_l [N,D] and the plain gather.
+// Dropout (training, drop_ratio > 0) follows every BatchNorm (+ReLU) as a
+// counter-based mask (dropout.h) recomputed wherever h_l is: in the apply that
+// stores it, in the next layer's gather, in the BatchNorm backward.  The
+// forward's first launch copies (seed, call counter) from drop_state into the
+// arena's dropkey slot and advances the counter; every kernel of the call,
+// and of its backward, reads the key from the arena.
 // Workspace: backward scratch dh, dz, dagg [N,D] + dz1 [N,2D], then the
 // largest workspace any called entry point asks for.
 #include "common.h"
@@ -40,7 +46,7 @@ struct ArenaLayout {
       h[MOLCLR_MAX_LAYERS], mean[MOLCLR_MAX_LAYERS], invstd[MOLCLR_MAX_LAYERS],
       coef[MOLCLR_MAX_LAYERS];
   size_t bits[MOLCLR_MAX_LAYERS];  // h3: ReLU mask of a1_l as bits [ceil(2D / 32)][N]
-  size_t h0, ec, smax, bmax, total;
+  size_t h0, ec, smax, bmax, dropkey, total;
   ArenaLayout(int L, int64_t N, int64_t D, size_t es) {
     size_t used = 0;
     auto off = [&](size_t bytes) {
@@ -63,6 +69,7 @@ struct ArenaLayout {
     smax = off((size_t)MOLCLR_MAX_LAYERS * 2 * kMaxSlotFloats * sizeof(float));  // h3: max |agg_l|, |a1_l|
     // h3: the backward's max |dz_l|, |dz1_l| (zeroed by the forward with smax)
     bmax = off((size_t)MOLCLR_MAX_LAYERS * 2 * kMaxSlotFloats * sizeof(float));
+    dropkey = off(2 * sizeof(int64_t));  // this forward's dropout key (seed, call)
     total = used;
   }
 };
@@ -91,8 +98,18 @@ size_t kernels_ws(int64_t N, int64_t D) {
 // backward scratch dh, dz, dagg [N,D] + dz1 [N,2D], in the storage type
 size_t scratch_bytes(int64_t N, int64_t D, size_t es) { return ((size_t)N * D * 3 + (size_t)N * 2 * D) * es; }
 
+// the dropout fields of either encoder struct
+int check_drop(const char* who, double drop_ratio, const int64_t* drop_state, int training) {
+  MOLCLR_REQUIRE(drop_ratio >= 0.0 && drop_ratio < 1.0, "%s: drop_ratio %g outside [0, 1)", who,
+                 drop_ratio);
+  MOLCLR_REQUIRE(!(training && drop_ratio > 0.0) || drop_state,
+                 "%s: training with dropout needs drop_state", who);
+  return MOLCLR_OK;
+}
+
 int check_encoder(const molclr_gin_encoder* e, const molclr_device_graph* g) {
   MOLCLR_REQUIRE(e && g, "gin_encoder: null encoder / graph");
+  MOLCLR_TRY_RC(check_drop("gin_encoder", e->drop_ratio, e->drop_state, e->training));
   MOLCLR_REQUIRE(e->num_layer >= 1 && e->num_layer <= MOLCLR_MAX_LAYERS,
                  "gin_encoder: num_layer %d", e->num_layer);
   MOLCLR_REQUIRE(e->dim > 0 && e->dim % 4 == 0, "gin_encoder: dim %lld", (long long)e->dim);
@@ -138,11 +155,17 @@ int graph_segments(const molclr_device_graph* g, const int64_t* N, SegRows& out)
   return MOLCLR_OK;
 }
 
-// the segmented BatchNorm of a graph, host- or device-sized
+// the segmented BatchNorm of a graph, host- or device-sized; drop: the dropout
+// after it (NULL: none)
 int seg_bn_fwd(const SegRows& sg, const void* z, const float* gamma, const float* beta,
                float* rmean, float* rvar, int64_t* nbt, void* y, float* mean, float* invstd,
                int64_t D, int dtype, double momentum, double eps, int training, int relu,
-               void* ws, size_t ws_bytes, molclr_stream_t stream) {
+               const DropArgs* drop, void* ws, size_t ws_bytes, molclr_stream_t stream) {
+  if (drop)
+    return molclr::batchnorm_seg_fwd_drop(z, gamma, beta, rmean, rvar, nbt, y, mean, invstd, sg.n,
+                                          sg.rows, sg.dev, sg.cap, D, dtype, momentum, eps,
+                                          training, relu, *drop, ws, ws_bytes,
+                                          molclr::as_stream(stream));
   if (sg.dev)
     return molclr_batchnorm_seg_fwd_dev(z, gamma, beta, rmean, rvar, nbt, y, mean, invstd, sg.n,
                                         sg.dev, sg.cap, D, dtype, momentum, eps, training, relu,
@@ -168,7 +191,13 @@ int seg_bn_coeffs(const SegRows& sg, const void* z, const float* gamma, const fl
 int seg_bn_bwd(const SegRows& sg, const void* dy, const void* z, const float* gamma,
                const float* beta, const float* mean, const float* invstd, void* dz, float* dgamma,
                float* dbeta, int64_t D, int dtype, int relu, int accumulate, float* rowmax,
-               float* slot, void* ws, size_t ws_bytes, molclr_stream_t stream) {
+               float* slot, const DropArgs* drop, void* ws, size_t ws_bytes,
+               molclr_stream_t stream) {
+  if (drop)
+    return molclr::batchnorm_seg_bwd_drop(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta,
+                                          sg.n, sg.rows, sg.dev, sg.cap, D, dtype, relu,
+                                          accumulate, rowmax, slot, *drop, ws, ws_bytes,
+                                          molclr::as_stream(stream));
   if (sg.dev)
     return molclr_batchnorm_seg_bwd_dev(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta, sg.n,
                                         sg.dev, sg.cap, D, dtype, relu, accumulate, rowmax, slot,
@@ -179,6 +208,27 @@ int seg_bn_bwd(const SegRows& sg, const void* dy, const void* z, const float* ga
                                         accumulate, rowmax, slot, ws, ws_bytes, stream);
   return molclr_batchnorm_seg_bwd(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta, sg.n,
                                   sg.rows, D, dtype, relu, accumulate, ws, ws_bytes, stream);
+}
+
+// This call's dropout: the key in the arena, opened by the forward
+// (open_drop); at(l): the arguments of the dropout after layer l's BatchNorm,
+// NULL when the call has none.
+struct CallDrop {
+  bool on;
+  double p;
+  const int64_t* key;
+  DropArgs cur;
+  CallDrop(int training, double drop_ratio, const void* key_slot)
+      : on(training && drop_ratio > 0.0), p(drop_ratio), key((const int64_t*)key_slot), cur{} {}
+  const DropArgs* at(int l) {
+    if (!on) return nullptr;
+    cur = make_drop_args(key, p, l);
+    return &cur;
+  }
+};
+int open_drop(const CallDrop& d, int64_t* state, molclr_stream_t stream) {
+  if (!d.on) return MOLCLR_OK;
+  return molclr_dropout_next_key(state, const_cast<int64_t*>(d.key), stream);
 }
 
 #define MOLCLR_TRY(expr)      \
@@ -257,6 +307,8 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
 
   // layer l > 0 gathers from z_{l-1} through coef_{l-1} (fused), else from h
   const bool fused = agg_bn();
+  CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);
+  MOLCLR_TRY(open_drop(drop, e->drop_state, stream));
   void* h = A + lay.h0;
   if (bf)
     MOLCLR_TRY(molclr_atom_embed_fwd_bf16(x, e->x_embedding1, e->x_embedding2, (uint16_t*)h, N, D,
@@ -280,7 +332,13 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
     const float* cp = bn_src ? F(lay.coef[l - 1]) : nullptr;
     if (bf) {
       uint16_t *agg = H(lay.agg[l]), *a1 = H(lay.a1[l]), *z = H(lay.z[l]);
-      if (bn_src)
+      if (bn_src && drop.on)
+        MOLCLR_TRY(molclr::gine_aggregate_bn_fwd_drop(zp, cp, 1, seg.n, seg.rows, seg.dev,
+                                                      g->rowptr, g->col, g->ecode, g->nbr, Ecl,
+                                                      agg, N, D, MOLCLR_DTYPE_BF16, nullptr,
+                                                      nullptr, *drop.at(l - 1),
+                                                      molclr::as_stream(stream)));
+      else if (bn_src)
         MOLCLR_TRY(molclr_gine_aggregate_bn_fwd_bf16((const uint16_t*)zp, cp, 1, seg.n, seg.rows,
                                                      seg.dev, g->rowptr, g->col, g->ecode, g->nbr,
                                                      Ecl, agg, N, D, stream));
@@ -308,12 +366,19 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
         MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                               e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
                               F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_BF16, e->momentum,
-                              e->eps, e->training, last ? 0 : 1, kws, kws_bytes, stream));
+                              e->eps, e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes,
+                              stream));
     } else {
       float *agg = F(lay.agg[l]), *a1 = F(lay.a1[l]), *z = F(lay.z[l]);
       float* sl = fmax + 2 * l * kMaxSlotFloats;
       // h3 forward: agg's row maxima from the aggregation itself, max |agg| from lin1
-      if (bn_src)
+      if (bn_src && drop.on)
+        MOLCLR_TRY(molclr::gine_aggregate_bn_fwd_drop(zp, cp, 1, seg.n, seg.rows, seg.dev,
+                                                      g->rowptr, g->col, g->ecode, g->nbr, Ecl,
+                                                      agg, N, D, MOLCLR_DTYPE_F32,
+                                                      h3f ? ragg : nullptr, nullptr,
+                                                      *drop.at(l - 1), molclr::as_stream(stream)));
+      else if (bn_src)
         MOLCLR_TRY(molclr_gine_aggregate_bn_fwd((const float*)zp, cp, 1, seg.n, seg.rows, seg.dev,
                                                 g->rowptr, g->col, g->ecode, g->nbr, Ecl, agg, N,
                                                 D, h3f ? ragg : nullptr, nullptr, stream));
@@ -367,7 +432,8 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
         MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                               e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
                               F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_F32, e->momentum,
-                              e->eps, e->training, last ? 0 : 1, kws, kws_bytes, stream));
+                              e->eps, e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes,
+                              stream));
     }
     h = y;
   }
@@ -412,6 +478,7 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
   const bool h3 = !bf && e->fp32_gemm != 0;
   const float* fmax = F(lay.smax);  // the forward's max |agg_l|, max |a1_l|
   // h3: bmax[l][0] = max |dz_l|, [l][1] = max |dz1_l|
+  CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);  // the forward's key
 
   const void* dy = dh_out;
   for (int l = L - 1; l >= 0; --l) {
@@ -426,12 +493,12 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
       // a block barrier)
       MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
                             F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D,
-                            MOLCLR_DTYPE_F32, last ? 0 : 1, 1, rdz, nullptr, kws, kws_bytes,
-                            stream));
+                            MOLCLR_DTYPE_F32, last ? 0 : 1, 1, rdz, nullptr, drop.at(l), kws,
+                            kws_bytes, stream));
     } else {
       MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
                             F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D, dt,
-                            last ? 0 : 1, 1, nullptr, nullptr, kws, kws_bytes, stream));
+                            last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws, kws_bytes, stream));
     }
     if (bf) {
       const uint16_t *hz = (const uint16_t*)dz, *ha1 = (const uint16_t*)a1;
@@ -546,7 +613,8 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
 // GCN encoder executor (models/gcn_molclr.py:140-151), same scheme: per layer
 // xw = x W (scratch), z = gcn_aggregate(xw) + bias (BatchNorm input, saved),
 // h = BatchNorm(z) (+ReLU but the last; the next layer's input, saved).
-// Arena: per layer z_l, h_l [N,D], mean_l / invstd_l [D]; then h0 [N,D].
+// Arena: per layer z_l, h_l [N,D], mean_l / invstd_l [D]; then h0 [N,D] and the
+// dropout key (as the GIN executor's).
 // Workspace: xw / dxw, dz, dh [N,D] x 3, then the entry points' largest.
 // ---------------------------------------------------------------------------
 namespace {
@@ -555,7 +623,7 @@ struct GcnArena {
   size_t z[MOLCLR_MAX_LAYERS], h[MOLCLR_MAX_LAYERS], mean[MOLCLR_MAX_LAYERS],
       invstd[MOLCLR_MAX_LAYERS];
   size_t hmax[MOLCLR_MAX_LAYERS];  // h3: max slot of layer l's input (floats, contiguous)
-  size_t h0, total;
+  size_t h0, dropkey, total;  // dropkey: this forward's dropout key (seed, call)
   GcnArena(int L, int64_t N, int64_t D) {
     size_t used = 0;
     auto off = [&](size_t count) {
@@ -572,6 +640,7 @@ struct GcnArena {
     const size_t slots = off((size_t)L * kMaxSlotFloats);
     for (int l = 0; l < L; ++l) hmax[l] = slots + (size_t)l * kMaxSlotFloats;
     h0 = off(N * D);
+    dropkey = off(2 * sizeof(int64_t) / sizeof(float));
     total = used * sizeof(float);
   }
 };
@@ -595,6 +664,7 @@ size_t gcn_h3_bytes(int64_t N) {
 
 int check_gcn(const molclr_gcn_encoder* e, const molclr_device_graph* g) {
   MOLCLR_REQUIRE(e && g, "gcn_encoder: null encoder / graph");
+  MOLCLR_TRY_RC(check_drop("gcn_encoder", e->drop_ratio, e->drop_state, e->training));
   MOLCLR_REQUIRE(e->num_layer >= 1 && e->num_layer <= MOLCLR_MAX_LAYERS,
                  "gcn_encoder: num_layer %d", e->num_layer);
   MOLCLR_REQUIRE(e->dim > 0 && e->dim % 4 == 0, "gcn_encoder: dim %lld", (long long)e->dim);
@@ -647,6 +717,8 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
     molclr::set_error("gcn_encoder_fwd: zeroing the max slots failed");
     return MOLCLR_ERR_ARG;
   }
+  CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);
+  MOLCLR_TRY(open_drop(drop, e->drop_state, stream));
   float* h = A + lay.h0;
   MOLCLR_TRY(molclr_atom_embed_fwd(x, e->x_embedding1, e->x_embedding2, h, N, D, e->n_atom,
                                    e->n_chiral, e->status, stream));
@@ -670,7 +742,7 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
     MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                           e->bn_running_var[l], e->bn_num_batches_tracked[l], y, A + lay.mean[l],
                           A + lay.invstd[l], D, MOLCLR_DTYPE_F32, e->momentum, e->eps,
-                          e->training, last ? 0 : 1, kws, kws_bytes, stream));
+                          e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes, stream));
     h = y;
   }
   return MOLCLR_OK;
@@ -705,6 +777,7 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
   void* kws = (char*)rdxw + gcn_h3_bytes(N);
   const size_t kws_bytes = gcn_kernels_ws(N, D);
   const bool h3 = e->fp32_gemm == 1;
+  CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);  // the forward's key
 
   const float* dy = dh_out;
   for (int l = L - 1; l >= 0; --l) {
@@ -714,8 +787,8 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
     MOLCLR_REQUIRE(gr->bn_weight[l] && gr->bn_bias[l], "gcn_encoder_bwd: BatchNorm grads needed");
     MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], A + lay.mean[l],
                           A + lay.invstd[l], dz, gr->bn_weight[l], gr->bn_bias[l], D,
-                          MOLCLR_DTYPE_F32, last ? 0 : 1, 1, nullptr, nullptr, kws, kws_bytes,
-                          stream));
+                          MOLCLR_DTYPE_F32, last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws,
+                          kws_bytes, stream));
     // ops._GCNConv.backward order: aggregation (dxw, edge tables, bias), dW, dx
     MOLCLR_TRY(molclr_gcn_aggregate_bwd(dz, g->rowptr_t, g->col_t, g->nbr_t, g->ecount, dxw,
                                         gr->edge_embedding1[l], gr->edge_embedding2[l],

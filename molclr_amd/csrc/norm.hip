@@ -2,7 +2,7 @@
 // BatchNorm1d(+ReLU) forward/backward, segment mean/add pooling, F.normalize.
 //
 // Reference: models/ginet_molclr.py:107-113 (BatchNorm1d in train mode, ReLU on
-// all but the last layer, dropout p = drop_ratio = 0, global_mean_pool),
+// all but the last layer, dropout p = drop_ratio -- dropout.h --, global_mean_pool),
 // molclr.py:63-64 (F.normalize).  Column statistics are reduced in a fixed
 // order (per-thread Welford -> per-block Chan merge -> per-column merge over
 // blocks), so every result is run-to-run deterministic.
@@ -356,13 +356,14 @@ __global__ void k_bn_eval_coeffs(const float* __restrict__ gamma, const float* _
 
 // U = 2 (bf16 storage): two column units per thread, one 16-byte access each
 // way (8-byte bf16 accesses ran at half the HBM rate of the fp32 form); the
-// same per-element arithmetic.  d4 % U == 0 (host).
-template <typename St, int U = 1>
+// same per-element arithmetic.  d4 % U == 0 (host).  DR = DropArgs: dropout
+// after the ReLU (dropout.h), before the store's rounding.
+template <typename St, int U = 1, typename DR = NoDrop>
 __global__ __launch_bounds__(kT) void k_bn_apply(const typename St::T* __restrict__ z,
                                                  const float4* __restrict__ scale,
                                                  const float4* __restrict__ shift,
                                                  typename St::T* __restrict__ y, int64_t total4,
-                                                 int d4, int relu, Segs sg) {
+                                                 int d4, int relu, Segs sg, DR dr) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total4 / U) return;
   const int64_t u0 = t * U;
@@ -383,6 +384,7 @@ __global__ __launch_bounds__(kT) void k_bn_apply(const typename St::T* __restric
     float4 o = make_float4(bn_apply1(v[j].x, sc.x, sh.x), bn_apply1(v[j].y, sc.y, sh.y),
                            bn_apply1(v[j].z, sc.z, sh.z), bn_apply1(v[j].w, sc.w, sh.w));
     if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+    if constexpr (DR::kOn) o = Drop<DR>(dr)(o, i, c + j);
     v[j] = o;
   }
   if constexpr (U == 2) St::st2(y, t, v[0], v[1]);
@@ -400,13 +402,15 @@ __device__ __forceinline__ void bn_coeffs4(const float* gamma, const float* beta
   bn_coeffs(g.w, b.w, mu.w, is.w, sc.w, sh.w);
 }
 
-template <typename St>
+// DR = DropArgs: dy is the gradient behind the dropout that followed the
+// (ReLU of the) BatchNorm output; its mask and scale join the ReLU mask.
+template <typename St, typename DR = NoDrop>
 __global__ void k_bn_bwd_partial(const typename St::T* __restrict__ dy,
                                  const typename St::T* __restrict__ z,
                                  const float4* __restrict__ mean, const float4* __restrict__ invstd,
                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                  int d4, int band, Segs sg, int relu, float4* __restrict__ p1,
-                                 float4* __restrict__ p2) {
+                                 float4* __restrict__ p2, DR dr) {
   extern __shared__ __attribute__((aligned(16))) float4 red[];  // [2][band][d4]
   const int tid = threadIdx.x;
   const bool live = tid < band * d4;
@@ -419,6 +423,7 @@ __global__ void k_bn_bwd_partial(const typename St::T* __restrict__ dy,
   if (end > at.row1) end = at.row1;
   float4 s1 = f4zero(), s2 = f4zero();
   if (live) {
+    const Drop<DR> drop(dr);
     float4 mu = mean[s * d4 + c], is = invstd[s * d4 + c], sc, sh;
     bn_coeffs4(gamma, beta, mu, is, c, sc, sh);
     // eight rows' loads in flight per round trip (few waves per CU here);
@@ -444,6 +449,7 @@ __global__ void k_bn_bwd_partial(const typename St::T* __restrict__ dy,
           g.z = bn_apply1(x.z, sc.z, sh.z) > 0.f ? g.z : 0.f;
           g.w = bn_apply1(x.w, sc.w, sh.w) > 0.f ? g.w : 0.f;
         }
+        if constexpr (DR::kOn) g = drop(g, i0 + (int64_t)u * band, c);
         s1 = f4add(s1, g);
         s2.x += g.x * ((x.x - mu.x) * is.x);
         s2.y += g.y * ((x.y - mu.y) * is.y);
@@ -532,14 +538,15 @@ __global__ __launch_bounds__(kRedCols* kRedLanes) void k_bn_bwd_final(
   }
 }
 
-// one float4 of dz from its dy / z units (segment s, column unit c)
+// one float4 of dz from its dy / z units (segment s, row i, column unit c)
+template <typename DR>
 __device__ __forceinline__ float4 bn_bwd_math(float4 g, float4 x, const float4* __restrict__ mean,
                                               const float4* __restrict__ invstd,
                                               const float* __restrict__ gamma,
                                               const float* __restrict__ beta,
                                               const float4* __restrict__ k1,
                                               const float4* __restrict__ k2, int s, int c, int d4,
-                                              int relu) {
+                                              int relu, const Drop<DR>& drop, int64_t i) {
   float4 mu = mean[s * d4 + c], is = invstd[s * d4 + c], sc, sh;
   bn_coeffs4(gamma, beta, mu, is, c, sc, sh);
   float4 a = k1[s * d4 + c], b = k2[s * d4 + c];
@@ -549,6 +556,7 @@ __device__ __forceinline__ float4 bn_bwd_math(float4 g, float4 x, const float4* 
     g.z = bn_apply1(x.z, sc.z, sh.z) > 0.f ? g.z : 0.f;
     g.w = bn_apply1(x.w, sc.w, sh.w) > 0.f ? g.w : 0.f;
   }
+  if constexpr (DR::kOn) g = drop(g, i, c);
   // dz = gamma*invstd * (g - mean(g) - xhat * mean(g*xhat))  (torch CPU BN backward)
   float4 o;
   o.x = (g.x - a.x - ((x.x - mu.x) * is.x) * b.x) * sc.x;
@@ -559,13 +567,13 @@ __device__ __forceinline__ float4 bn_bwd_math(float4 g, float4 x, const float4* 
 }
 
 // one float4 of dz (k_bn_bwd_apply), stored and returned
-template <typename St>
+template <typename St, typename DR>
 __device__ __forceinline__ float4 bn_bwd_elem(
     const typename St::T* __restrict__ dy, const typename St::T* __restrict__ z,
     const float4* __restrict__ mean, const float4* __restrict__ invstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float4* __restrict__ k1,
     const float4* __restrict__ k2, typename St::T* __restrict__ dz, int64_t t, int d4, int relu,
-    Segs sg, int64_t total4) {
+    Segs sg, int64_t total4, const DR& dr) {
   const int64_t i = row_of(t, d4, total4);
   const int c = (int)(t - i * d4);
   const int s = seg_of_row(sg, i);
@@ -573,20 +581,20 @@ __device__ __forceinline__ float4 bn_bwd_elem(
     St::st(dz, t, f4zero());
     return f4zero();
   }
-  const float4 o = bn_bwd_math(St::ld(dy, t), St::ld(z, t), mean, invstd, gamma, beta, k1, k2, s,
-                               c, d4, relu);
+  const float4 o = bn_bwd_math<DR>(St::ld(dy, t), St::ld(z, t), mean, invstd, gamma, beta, k1, k2,
+                                   s, c, d4, relu, Drop<DR>(dr), i);
   St::st(dz, t, o);
   return o;
 }
 
 // two column units per thread, 16-byte accesses (bf16 storage, no row maxima)
-template <typename St>
+template <typename St, typename DR = NoDrop>
 __global__ __launch_bounds__(kT) void k_bn_bwd_apply2(
     const typename St::T* __restrict__ dy, const typename St::T* __restrict__ z,
     const float4* __restrict__ mean, const float4* __restrict__ invstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float4* __restrict__ k1,
     const float4* __restrict__ k2, typename St::T* __restrict__ dz, int64_t total4, int d4,
-    int relu, Segs sg) {
+    int relu, Segs sg, DR dr) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total4 / 2) return;
   const int64_t u0 = 2 * t;
@@ -600,17 +608,18 @@ __global__ __launch_bounds__(kT) void k_bn_bwd_apply2(
   float4 g0, g1, x0, x1;
   St::ld2(dy, t, g0, g1);
   St::ld2(z, t, x0, x1);
-  St::st2(dz, t, bn_bwd_math(g0, x0, mean, invstd, gamma, beta, k1, k2, s, c, d4, relu),
-          bn_bwd_math(g1, x1, mean, invstd, gamma, beta, k1, k2, s, c + 1, d4, relu));
+  const Drop<DR> drop(dr);
+  St::st2(dz, t, bn_bwd_math<DR>(g0, x0, mean, invstd, gamma, beta, k1, k2, s, c, d4, relu, drop, i),
+          bn_bwd_math<DR>(g1, x1, mean, invstd, gamma, beta, k1, k2, s, c + 1, d4, relu, drop, i));
 }
 
-template <typename St>
+template <typename St, typename DR = NoDrop>
 __global__ __launch_bounds__(kT) void k_bn_bwd_apply(
     const typename St::T* __restrict__ dy, const typename St::T* __restrict__ z,
     const float4* __restrict__ mean, const float4* __restrict__ invstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float4* __restrict__ k1,
     const float4* __restrict__ k2, typename St::T* __restrict__ dz, int64_t total4, int d4,
-    int relu, Segs sg, float* __restrict__ rowparts, int nparts, float* __restrict__ slot) {
+    int relu, Segs sg, float* __restrict__ rowparts, int nparts, float* __restrict__ slot, DR dr) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (rowparts != nullptr) {  // block-uniform: every thread reaches the reductions
     // dz's row maxima as row parts (row_max_parts) and its max
@@ -618,8 +627,8 @@ __global__ __launch_bounds__(kT) void k_bn_bwd_apply(
     float m = 0.f;
     int row = -1;
     if (t < total4) {
-      const float4 o = bn_bwd_elem<St>(dy, z, mean, invstd, gamma, beta, k1, k2, dz, t, d4, relu,
-                                       sg, total4);
+      const float4 o = bn_bwd_elem<St, DR>(dy, z, mean, invstd, gamma, beta, k1, k2, dz, t, d4,
+                                           relu, sg, total4, dr);
       m = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)));
       row = (int)row_of(t, d4, total4);
     }
@@ -628,7 +637,7 @@ __global__ __launch_bounds__(kT) void k_bn_bwd_apply(
     return;
   }
   if (t >= total4) return;
-  bn_bwd_elem<St>(dy, z, mean, invstd, gamma, beta, k1, k2, dz, t, d4, relu, sg, total4);
+  bn_bwd_elem<St, DR>(dy, z, mean, invstd, gamma, beta, k1, k2, dz, t, d4, relu, sg, total4, dr);
 }
 
 
@@ -941,7 +950,7 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
            float* running_var, int64_t* nbt, void* yv, float* save_mean, float* save_invstd,
            int nseg, const int64_t* seg_rows, int64_t D, double momentum, double eps, int training,
            int relu, void* workspace, size_t workspace_bytes, hipStream_t s,
-           const int64_t* drows = nullptr, int64_t cap = 0) {
+           const int64_t* drows = nullptr, int64_t cap = 0, const DropArgs* drop = nullptr) {
   BnPlan plan;
   if (int rc = bn_fwd_coeffs<St>(zv, gamma, beta, running_mean, running_var, nbt, save_mean,
                                  save_invstd, nullptr, nseg, seg_rows, D, momentum, eps, training,
@@ -953,14 +962,19 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
   const float *scale = plan.scale, *shift = plan.shift;
   const int64_t total4 = plan.rows * (D / 4);
   if (total4 > 0 && y) {  // y == NULL: statistics only (the consumer applies them)
-    if (St::kBytes == 2 && D % 8 == 0)
-      hipLaunchKernelGGL((k_bn_apply<St, 2>), dim3(molclr::ceil_div(total4 / 2, kT)), dim3(kT), 0,
-                         s, z, (const float4*)scale, (const float4*)shift, y, total4, (int)(D / 4),
-                         relu, sg);
-    else
-      hipLaunchKernelGGL((k_bn_apply<St, 1>), dim3(molclr::ceil_div(total4, kT)), dim3(kT), 0, s,
-                         z, (const float4*)scale, (const float4*)shift, y, total4, (int)(D / 4),
-                         relu, sg);
+    auto apply = [&](auto dr) {
+      using DR = decltype(dr);
+      if (St::kBytes == 2 && D % 8 == 0)
+        hipLaunchKernelGGL((k_bn_apply<St, 2, DR>), dim3(molclr::ceil_div(total4 / 2, kT)),
+                           dim3(kT), 0, s, z, (const float4*)scale, (const float4*)shift, y,
+                           total4, (int)(D / 4), relu, sg, dr);
+      else
+        hipLaunchKernelGGL((k_bn_apply<St, 1, DR>), dim3(molclr::ceil_div(total4, kT)), dim3(kT),
+                           0, s, z, (const float4*)scale, (const float4*)shift, y, total4,
+                           (int)(D / 4), relu, sg, dr);
+    };
+    if (drop) apply(*drop);
+    else apply(NoDrop{});
   }
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
@@ -974,7 +988,8 @@ int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* bet
            const float* save_mean, const float* save_invstd, void* dzv, float* dgamma,
            float* dbeta, int nseg, const int64_t* seg_rows, int64_t D, int relu, int accumulate,
            void* workspace, size_t workspace_bytes, hipStream_t s, float* rowparts = nullptr,
-           float* slot = nullptr, const int64_t* drows = nullptr, int64_t cap = 0) {
+           float* slot = nullptr, const int64_t* drows = nullptr, int64_t cap = 0,
+           const DropArgs* drop = nullptr) {
   Segs sg;
   int64_t P = 0, rows = 0;
   if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
@@ -997,23 +1012,30 @@ int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* bet
   float* k2 = w.take<float>(nseg * D);
   // the forward's coefficient expression is recomputed in-kernel (same ReLU mask)
   const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
-  hipLaunchKernelGGL(k_bn_bwd_partial<St>, dim3((unsigned)P), dim3(b.threads), lds, s, dy, z,
-                     (const float4*)save_mean, (const float4*)save_invstd, gamma, beta, b.d4,
-                     b.band, sg, relu, (float4*)p1, (float4*)p2);
-  hipLaunchKernelGGL(k_bn_bwd_final, dim3(molclr::ceil_div(D, kRedCols)), dim3(kRedCols * kRedLanes),
-                     0, s, p1, p2, sg, D, dgamma, dbeta, k1, k2, accumulate);
   const int64_t total4 = rows * (D / 4);
   static_assert(kT % 64 == 0, "row parts follow the waves");
   MOLCLR_REQUIRE(!rowparts || rows < (1ll << 31), "batchnorm_seg_bwd_max: too many rows");
-  if (St::kBytes == 2 && D % 8 == 0 && !rowparts && !slot)
-    hipLaunchKernelGGL(k_bn_bwd_apply2<St>, dim3(molclr::ceil_div(total4 / 2, kT)), dim3(kT), 0, s,
-                       dy, z, (const float4*)save_mean, (const float4*)save_invstd, gamma, beta,
-                       (const float4*)k1, (const float4*)k2, dz, total4, (int)(D / 4), relu, sg);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_apply<St>, dim3(molclr::ceil_div(total4, kT)), dim3(kT), 0, s, dy,
-                       z, (const float4*)save_mean, (const float4*)save_invstd, gamma, beta,
-                       (const float4*)k1, (const float4*)k2, dz, total4, (int)(D / 4), relu, sg,
-                       rowparts, bn_row_parts(D), slot);
+  auto launch = [&](auto dr) {
+    using DR = decltype(dr);
+    hipLaunchKernelGGL((k_bn_bwd_partial<St, DR>), dim3((unsigned)P), dim3(b.threads), lds, s, dy,
+                       z, (const float4*)save_mean, (const float4*)save_invstd, gamma, beta, b.d4,
+                       b.band, sg, relu, (float4*)p1, (float4*)p2, dr);
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(molclr::ceil_div(D, kRedCols)),
+                       dim3(kRedCols * kRedLanes), 0, s, p1, p2, sg, D, dgamma, dbeta, k1, k2,
+                       accumulate);
+    if (St::kBytes == 2 && D % 8 == 0 && !rowparts && !slot)
+      hipLaunchKernelGGL((k_bn_bwd_apply2<St, DR>), dim3(molclr::ceil_div(total4 / 2, kT)),
+                         dim3(kT), 0, s, dy, z, (const float4*)save_mean,
+                         (const float4*)save_invstd, gamma, beta, (const float4*)k1,
+                         (const float4*)k2, dz, total4, (int)(D / 4), relu, sg, dr);
+    else
+      hipLaunchKernelGGL((k_bn_bwd_apply<St, DR>), dim3(molclr::ceil_div(total4, kT)), dim3(kT), 0,
+                         s, dy, z, (const float4*)save_mean, (const float4*)save_invstd, gamma,
+                         beta, (const float4*)k1, (const float4*)k2, dz, total4, (int)(D / 4),
+                         relu, sg, rowparts, bn_row_parts(D), slot, dr);
+  };
+  if (drop) launch(*drop);
+  else launch(NoDrop{});
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
@@ -1184,6 +1206,45 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_dev(const void* dy, const void* z, const
   return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
                         nullptr, D, relu, accumulate, workspace, workspace_bytes, s, nullptr,
                         nullptr, seg_rows_dev, rows_cap);
+}
+
+// The encoder executors' BatchNorm with dropout after it (dropout.h): the
+// entry points above -- host-sized segments (seg_rows) or device-sized ones
+// (seg_rows_dev, rows_cap rows) -- with the mask applied where the ReLU is.
+int molclr::batchnorm_seg_fwd_drop(const void* z, const float* gamma, const float* beta,
+                                   float* running_mean, float* running_var,
+                                   int64_t* num_batches_tracked, void* y, float* save_mean,
+                                   float* save_invstd, int nseg, const int64_t* seg_rows,
+                                   const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D,
+                                   int dtype, double momentum, double eps, int training, int relu,
+                                   const DropArgs& drop, void* workspace, size_t workspace_bytes,
+                                   hipStream_t s) {
+  if (dtype == MOLCLR_DTYPE_F32)
+    return bn_fwd<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
+                         save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
+                         workspace, workspace_bytes, s, seg_rows_dev, rows_cap, &drop);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_fwd_drop: dtype %d", dtype);
+  return bn_fwd<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
+                        save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
+                        workspace, workspace_bytes, s, seg_rows_dev, rows_cap, &drop);
+}
+
+int molclr::batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* gamma,
+                                   const float* beta, const float* save_mean,
+                                   const float* save_invstd, void* dz, float* dgamma, float* dbeta,
+                                   int nseg, const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                   int64_t rows_cap, int64_t D, int dtype, int relu, int accumulate,
+                                   float* rowmax, float* slot, const DropArgs& drop,
+                                   void* workspace, size_t workspace_bytes, hipStream_t s) {
+  MOLCLR_REQUIRE(!rowmax || dtype == MOLCLR_DTYPE_F32, "batchnorm_seg_bwd_drop: row maxima are fp32 only");
+  if (dtype == MOLCLR_DTYPE_F32)
+    return bn_bwd<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
+                         seg_rows, D, relu, accumulate, workspace, workspace_bytes, s, rowmax, slot,
+                         seg_rows_dev, rows_cap, &drop);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_bwd_drop: dtype %d", dtype);
+  return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
+                        seg_rows, D, relu, accumulate, workspace, workspace_bytes, s, nullptr,
+                        nullptr, seg_rows_dev, rows_cap, &drop);
 }
 
 MOLCLR_API int molclr_batchnorm_fwd(const float* z, const float* gamma, const float* beta,

@@ -24,6 +24,23 @@ num_bond_type = 5  # including aromatic and self-loop edge
 num_bond_direction = 3
 
 
+def dropout_seed(generator: torch.Generator | None = None, rank: int = 0) -> int:
+    """The seed of an encoder's dropout stream: one draw from ``generator``
+    (torch's default CPU generator when None, so torch.manual_seed makes runs
+    repeatable), xor-ed with rank * 0x9E3779B97F4A7C15 so that the ranks of a
+    data-parallel run draw different masks.  Returned as a signed 64-bit
+    value (the stream takes its bit pattern)."""
+    draw = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.long,
+                             generator=generator).item())
+    seed = (draw ^ (int(rank) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def _rank() -> int:
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 class Encoder(nn.Module):
     """Atom embeddings, ``num_layer`` x (conv, BatchNorm), pooling, feat_lin
     (models/ginet_molclr.py:50-117, models/gcn_molclr.py:94-158) and the
@@ -61,6 +78,11 @@ class Encoder(nn.Module):
         self.emb_dim = emb_dim
         self.feat_dim = feat_dim
         self.drop_ratio = drop_ratio
+        # int64 [seed, call counter] of the executor's dropout stream on the
+        # parameters' device, made by the first training forward that needs it
+        # (_dropout_state).  A plain attribute, not a buffer: no part of
+        # state_dict().  dropout_state[1] = k replays call k's masks.
+        self.dropout_state = None
 
         self.x_embedding1 = nn.Embedding(num_atom_type, emb_dim)
         self.x_embedding2 = nn.Embedding(num_chirality_tag, emb_dim)
@@ -93,7 +115,8 @@ class Encoder(nn.Module):
 
     # Run the node-embedding stack through the native encoder executor (one
     # host call per direction) when its BatchNorm and dropout settings are the
-    # ones it implements; else op by op.
+    # ones it implements (dropout: any drop_ratio < 1, the masks drawn inside
+    # the executor's kernels); else op by op.
     use_executor = True
 
     def _executor_ok(self) -> bool:
@@ -101,7 +124,7 @@ class Encoder(nn.Module):
         # multiple (_dim_pad) with zero columns
         if not self.use_executor or self.num_layer > 16:
             return False
-        if self.drop_ratio > 0 and self.training:
+        if self.drop_ratio >= 1 and self.training:  # F.dropout's all-zero output: per op
             return False
         bn0 = self.batch_norms[0]
         return all(bn.track_running_stats and bn.affine and bn.momentum is not None
@@ -129,6 +152,17 @@ class Encoder(nn.Module):
         return [t if m is None else F.pad(t, tuple(k * p for k in m))
                 for t, m in zip(params, pads)]
 
+    def _dropout_state(self):
+        """dropout_state for this forward: None when no dropout applies."""
+        if not (self.training and self.drop_ratio > 0):
+            return None
+        dev = self.x_embedding1.weight.device
+        if self.dropout_state is None:
+            self.dropout_state = torch.tensor([dropout_seed(rank=_rank()), 0], dtype=torch.long)
+        if self.dropout_state.device != dev:
+            self.dropout_state = self.dropout_state.to(dev)
+        return self.dropout_state
+
     def _run_encoder(self, x, graph):
         """The executor on the (padded) width; returns h [N, emb_dim + pad]."""
         p = self._dim_pad()
@@ -149,10 +183,10 @@ class Encoder(nn.Module):
             return (h[:, :self.emb_dim] if self._dim_pad() else h), graph
         if self.precision != 'fp32':
             raise NotImplementedError("bf16 runs through the encoder executor only "
-                                      "(dropout 0, tracked BatchNorm statistics)")
+                                      "(tracked BatchNorm statistics)")
         if self._dim_pad():
             raise NotImplementedError("emb_dim % 4 != 0 runs through the encoder executor only "
-                                      "(dropout 0, tracked BatchNorm statistics)")
+                                      "(tracked BatchNorm statistics)")
         h = ops.atom_embed(data.x, self.x_embedding1.weight, self.x_embedding2.weight,
                            graph.status)
         step = self._layer_step(graph)

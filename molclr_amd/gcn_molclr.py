@@ -87,7 +87,8 @@ class GCN(Encoder):
     _LAYER_PADS = ((0, 1, 0, 1), (0, 1), None, None, (0, 1), (0, 1))
 
     def _executor(self, x, graph, bns, params):
-        return ops.gcn_encoder(x, graph, bns, params)
+        return ops.gcn_encoder(x, graph, bns, params, drop_ratio=self.drop_ratio,
+                               drop_state=self._dropout_state())
 
     def _layer_step(self, graph):
         return lambda l, h: self.gnns[l].conv(h, graph)

@@ -8,8 +8,8 @@ feat/2), act) x (pred_n_layer - 1), Linear(feat/2, 2 | 1) with act Softplus or
 ReLU; no ``out_lin``.  ``load_my_state_dict`` copies the entries of a
 pre-training checkpoint the model has and skips the rest (``out_lin.*``).
 
-The encoder is ginet_molclr.GINet's, run as it runs there (the executor with
-dropout 0 or in eval mode, op by op with F.dropout otherwise); everything
+The encoder is ginet_molclr.GINet's, run as it runs there (the executor,
+which draws the dropout masks of ``drop_ratio`` inside its kernels); everything
 after the pooling -- feat_lin, the head and, through :meth:`GINet.loss`, the
 criterion -- is ONE ops.task_head call (task_head.hip).
 """

@@ -88,7 +88,8 @@ class GINet(Encoder):
     _LAYER_PADS = ((0, 1, 0, 2), (0, 2), (0, 2, 0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1))
 
     def _executor(self, x, graph, bns, params):
-        return ops.gin_encoder(x, graph, bns, params, self.precision)
+        return ops.gin_encoder(x, graph, bns, params, self.precision,
+                               drop_ratio=self.drop_ratio, drop_state=self._dropout_state())
 
     def _layer_step(self, graph):
         # per-edge embeddings E1[bt] + E2[bd] of every layer, tabulated in one launch

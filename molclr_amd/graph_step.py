@@ -272,7 +272,7 @@ class CapturedTrainStep:
         if not self.model._executor_ok() or self.model._dim_pad():
             raise NotImplementedError(
                 "CapturedTrainStep: the model must run through the encoder executor with "
-                "emb_dim a multiple of the kernels' width (dropout 0, tracked BatchNorm)")
+                "emb_dim a multiple of the kernels' width (tracked BatchNorm)")
         ops._check_no_timer()
         graph = StagedPairGraph(self.device, key[0], key[1], key[2:])
         if pair is not None:

@@ -1179,10 +1179,14 @@ class _Encoder(torch.autograd.Function):
     """A whole node-embedding stack (ginet_molclr.py:98-111,
     gcn_molclr.py:140-151) through <kind.symbol>_fwd / _bwd (encoder.hip): the
     same kernels as the per-op path in the same order, one host call each way.
-    params: x_embedding1, x_embedding2, then per layer kind.layer_params."""
+    params: x_embedding1, x_embedding2, then per layer kind.layer_params.
+    drop: None, or (drop_ratio, drop_state) -- dropout after every BatchNorm
+    while training, drop_state the int64 [seed, call counter] on the device
+    (the forward advances the counter; the backward reuses its forward's key,
+    which the forward left in the arena)."""
 
     @staticmethod
-    def forward(ctx, kind: _EncoderKind, x_idx, graph: DeviceGraph, bns, dtype, *params):
+    def forward(ctx, kind: _EncoderKind, x_idx, graph: DeviceGraph, bns, dtype, drop, *params):
         _check(x_idx, *params)
         L = len(bns)
         D = params[0].shape[1]
@@ -1206,6 +1210,14 @@ class _Encoder(torch.autograd.Function):
             nbt = bn.num_batches_tracked
             enc.bn_num_batches_tracked[l] = nbt.data_ptr() if training and nbt is not None else None
         kind.fill(enc, layers, N, D, dtype)
+        if training and drop is not None and drop[0] > 0:
+            ratio, state = drop
+            if state is None or state.dtype != torch.long or state.numel() != 2 \
+                    or state.device != x_idx.device or not state.is_contiguous():
+                raise ValueError("molclr_amd: drop_state must be a contiguous int64 [2] tensor "
+                                 "(seed, call counter) on the inputs' device")
+            enc.drop_ratio, enc.drop_state = float(ratio), state.data_ptr()
+            ctx.drop_state = state  # the struct holds its address
         dev = x_idx.device
         sizes = (L, N, D, dtype) if kind.sized_by_dtype else (L, N, D)
         arena_bytes = _wsq(kind.symbol + "_arena_bytes", *sizes)
@@ -1262,19 +1274,35 @@ class _Encoder(torch.autograd.Function):
             for _ in range(L):
                 kind.account(ctx.enc, ctx.graph, N, D, ctx.dtype, True)
         ctx.arena = None
-        return (None, None, None, None, None, *ret)
+        return (None, None, None, None, None, None, *ret)
 
 
-def gcn_encoder(x_idx, graph, bns, params):
-    """GCN.encode through the encoder executor (see _Encoder)."""
-    return _Encoder.apply(_GCN, x_idx, graph, bns, _lib.DTYPE_F32, *params)
+def gcn_encoder(x_idx, graph, bns, params, drop_ratio: float = 0.0, drop_state=None):
+    """GCN.encode through the encoder executor (see _Encoder).  drop_ratio in
+    (0, 1) while training: dropout after every BatchNorm, its masks drawn from
+    drop_state (int64 [seed, call counter] on the device)."""
+    return _Encoder.apply(_GCN, x_idx, graph, bns, _lib.DTYPE_F32, (drop_ratio, drop_state),
+                          *params)
 
 
-def gin_encoder(x_idx, graph, bns, params, precision: str = "fp32"):
+def gin_encoder(x_idx, graph, bns, params, precision: str = "fp32", drop_ratio: float = 0.0,
+                drop_state=None):
     """GINet.encode through the encoder executor (see _Encoder); precision
     "bf16" runs the c5 configuration's bf16 storage / bf16 MFMA path and
-    returns bf16 node embeddings."""
-    return _Encoder.apply(_GIN, x_idx, graph, bns, DTYPES[precision], *params)
+    returns bf16 node embeddings.  drop_ratio / drop_state: as gcn_encoder."""
+    return _Encoder.apply(_GIN, x_idx, graph, bns, DTYPES[precision], (drop_ratio, drop_state),
+                          *params)
+
+
+def dropout_mask(drop_state, layer: int, p: float, N: int, D: int) -> torch.Tensor:
+    """The [N, D] uint8 keep-mask (1 kept, 0 dropped) the executors' kernels
+    apply after layer ``layer``'s BatchNorm in the call whose key is
+    ``drop_state`` = int64 [seed, call counter] (molclr_dropout_mask)."""
+    _check(drop_state)
+    keep = torch.empty(N, D, dtype=torch.uint8, device=drop_state.device)
+    _lib.call("molclr_dropout_mask", _c(drop_state).data_ptr(), int(layer), float(p),
+              keep.data_ptr(), N, D, _stream(drop_state))
+    return keep
 
 
 # public functional API -------------------------------------------------------
