@@ -1170,6 +1170,50 @@ int molclr_task_head_fwd(const molclr_task_head* head, void* workspace, size_t w
 int molclr_task_head_bwd(const molclr_task_head* head, const molclr_task_head_grads* grads,
                          void* workspace, size_t workspace_bytes, molclr_stream_t stream);
 
+/* ---- Motif readout (fine-tuning, motif model) --------------------------------
+ * models/ginet_finetune_mp.py:158-160: PyG 1.6.3's GlobalAttention(gate_nn =
+ * Linear(F, 1)) over cat(motif_embedding(clique_idx), h) by mol_idx.  B
+ * molecules; the T motif items are clique_idx int64 [T] with mol_ptr int32
+ * [B + 1] (0 = p_0 <= ... <= p_B = T), so the rows of segment b are
+ * E[clique_idx[i]] for i in [p_b, p_{b+1}) in order, then h[b] LAST (the
+ * reference appends the h rows after all motif rows).  gate g = x.w + c,
+ * alpha = exp(g - max_seg g) / sum_seg exp(g - max), a[b] = sum alpha_i x_i in
+ * that row order (PyG's + 1e-16 on a sum that is at least 1 vanishes in fp32
+ * and is omitted).  h, a [B, F], E [num_motifs, F], w [F], c [1] dense fp32;
+ * alpha [T + B]: the items' weights, then the h rows' -- saved for the backward.
+ * Any F >= 1 (16-byte accesses when F % 4 == 0 and the pointers allow), any
+ * number of items per molecule (none: a[b] = h[b]), repeated motif ids.
+ * A clique_idx outside [0, num_motifs) or a mol_ptr that breaks the rule
+ * above is never used as an index: it sets MOLCLR_STATUS_MOTIF_RANGE in
+ * *status (nullable) and that molecule's a row (and gradients) are NaN.
+ * Forward: one launch, one workgroup per molecule.  Backward: two launches --
+ * per molecule s_i = da.x_i, t = sum alpha_i s_i, dgate_i = alpha_i (s_i - t)
+ * (computed as alpha_i da.(x_i - a[b]) from the forward's a: no cancellation),
+ * dh[b] = alpha_h da[b] + dgate_h w; then one grid for dE[m] = sum over the
+ * items of motif m of (alpha_i da[mol(i)] + dgate_i w), dw = sum dgate_i x_i
+ * and dc = sum dgate_i.  dE needs the items grouped by motif id: sorted_idx
+ * (clique_idx in ascending order) and order (the item at each sorted position)
+ * of a STABLE sort, so every sum runs in ascending item order (dw and dc:
+ * within a molecule, then over the molecules).  No floating-point atomics:
+ * results are bit-identical from run to run.  acc_* add into dE / dweight /
+ * dbias instead of overwriting; without acc_dE the rows of E that no item uses
+ * are zeroed.  A NULL dh, dE, dweight or dbias is not computed.  The backward
+ * takes a workspace of molclr_motif_pool_workspace_bytes (0 for invalid
+ * sizes); nothing allocates or synchronises. */
+#define MOLCLR_STATUS_MOTIF_RANGE 32 /* status bit: motif id / mol_ptr out of range */
+size_t molclr_motif_pool_workspace_bytes(int64_t B, int64_t T, int64_t F);
+int molclr_motif_pool_fwd(const float* h, const float* E, const int64_t* clique_idx,
+                          const int32_t* mol_ptr, const float* gate_weight, const float* gate_bias,
+                          int64_t B, int64_t T, int64_t F, int64_t num_motifs, float* a,
+                          float* alpha, int32_t* status, molclr_stream_t stream);
+int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
+                          const int64_t* clique_idx, const int32_t* mol_ptr,
+                          const int64_t* sorted_idx, const int64_t* order, const float* gate_weight,
+                          const float* a, const float* alpha, int64_t B, int64_t T, int64_t F, int64_t num_motifs,
+                          float* dh, float* dE, float* dweight, float* dbias, int acc_dE,
+                          int acc_dweight, int acc_dbias, void* workspace, size_t workspace_bytes,
+                          molclr_stream_t stream);
+
 /* ---- Benchmark instrumentation (no reference counterpart) -------------------
  * Opt-in kernel timer.  While a kind is enabled, its launches go through
  * hipExtLaunchKernelGGL with a start/stop event pair recorded by the dispatch

@@ -209,6 +209,10 @@ def raise_for_status(st: int) -> None:
         if st & _lib.STATUS_LABEL_RANGE:
             what.append("class label outside [0, number of classes) "
                         "(the reference's CrossEntropyLoss raises)")
+        if st & _lib.STATUS_MOTIF_RANGE:
+            what.append("motif index outside the motif embedding table, or molecule "
+                        "segments of the motif items not ascending "
+                        "(the reference's nn.Embedding raises IndexError)")
         raise ValueError("invalid graph batch: " + ", ".join(what))
 
 

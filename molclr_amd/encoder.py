@@ -88,6 +88,7 @@ class Encoder(nn.Module):
         self.x_embedding2 = nn.Embedding(num_chirality_tag, emb_dim)
         nn.init.xavier_uniform_(self.x_embedding1.weight.data)
         nn.init.xavier_uniform_(self.x_embedding2.weight.data)
+        self._init_after_atom_embeddings()
 
         self.gnns = nn.ModuleList()
         for _ in range(num_layer):
@@ -104,6 +105,10 @@ class Encoder(nn.Module):
         self.pool = pool
 
         self.feat_lin = nn.Linear(self.emb_dim, self.feat_dim)
+
+    def _init_after_atom_embeddings(self):
+        """Modules a model creates between the atom embeddings and the GIN /
+        GCN layers (the motif model's motif_embedding); none by default."""
 
     def _init_projection_head(self):
         """out_lin of the pre-training models (ginet_molclr.py:92-96)."""

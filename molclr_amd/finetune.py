@@ -13,11 +13,16 @@ final test on the reloaded checkpoint that leaves ``self.roc_auc``,
 Differences: the criterion is computed inside the task head's launch
 (``model.loss``: ops.task_head); one :class:`FusedAdam` per learning-rate group;
 the metrics are numpy (no scikit-learn); ``model_type: gin`` trains
-ginet_finetune.GINet -- the reference goes on to a motif model there
-(ginet_finetune_mp.py, BRICS fragments through RDKit), which is not provided;
-optional keys ``log_root``, ``ckpt_root`` and ``seed``.  Invalid inputs (graph
-indices, atom features, class labels) raise at the next log step
-(``check_inputs``), as in molclr_amd.molclr.
+ginet_finetune.GINet, and the motif model the reference goes on to there
+(ginet_finetune_mp.py) is ``model_type: gin_motif``: as finetune.py:144-161,
+the plain model embeds the motif vocabulary, then ginet_finetune_mp.GINet is
+built, loaded and given those rows as its motif table.  The motifs come from
+the optional key ``motifs``: ``builtin`` (molclr_amd.motifs' fragmenter, no
+RDKit, parity unpinned; the default) or the path of a JSON export of the
+reference's BRICS cliques.  Optional keys ``log_root``, ``ckpt_root`` and
+``seed``.  Invalid inputs (graph indices, atom features, class labels, motif
+indices) raise at the next log step (``check_inputs``), as in
+molclr_amd.molclr.
 """
 from __future__ import annotations
 
@@ -132,6 +137,7 @@ class FineTune(object):
         else:
             raise ValueError("dataset.task must be 'classification' or 'regression'")
         self.normalizer = None
+        self.vocabulary = self.assignments = None  # model_type: gin_motif (load_motifs)
         # sticky OR of every step's graph + head status word (check_inputs)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
 
@@ -157,9 +163,55 @@ class FineTune(object):
                               "no reduced-precision path; training in fp32", RuntimeWarning,
                               stacklevel=2)
             model = GCN(task, **mcfg).to(self.device)
+        elif self.config['model_type'] == 'gin_motif':
+            return self._build_motif_model(task, mcfg)
         else:
             raise ValueError('Undefined GNN model.')
         return self._load_pre_trained_weights(model)
+
+    # -- the motif model (model_type: gin_motif) ------------------------------------
+    def load_motifs(self, smiles_data):
+        """The motif vocabulary and every molecule's motif indices, from the
+        config's ``motifs`` source (molclr_amd.motifs)."""
+        from .motifs import load_motifs
+        self.vocabulary, self.assignments = load_motifs(self.config.get('motifs', 'builtin'),
+                                                        smiles_data)
+
+    def embed_vocabulary(self, model):
+        """``(rows, h)``: the plain model's ``h`` of the vocabulary's graphs in
+        batches of ``batch_size``, in vocabulary order and in training mode as
+        finetune.py:149-156 (batch statistics, dropout active), under no_grad;
+        ``rows`` are the motifs that have a graph."""
+        from .data import Batch, Data
+        rows = [i for i, m in enumerate(self.vocabulary) if m.graph is not None]
+        feats = []
+        with torch.no_grad():
+            for k in range(0, len(rows), self.config['batch_size']):
+                graphs = [self.vocabulary[i].graph for i in rows[k:k + self.config['batch_size']]]
+                batch = Batch.from_data_list([
+                    Data(x=torch.from_numpy(g.x), edge_index=torch.from_numpy(g.edge_index),
+                         edge_attr=torch.from_numpy(g.edge_attr)) for g in graphs])
+                feats.append(model(batch.to(self.device))[0])
+        h = torch.cat(feats) if feats else torch.zeros(0, model.feat_dim, device=self.device)
+        return torch.tensor(rows, dtype=torch.long, device=self.device), h
+
+    def _build_motif_model(self, task, mcfg):
+        """finetune.py:144-161: the plain model embeds the vocabulary, the motif
+        model starts from those rows."""
+        from .ginet_finetune import GINet as PlainGINet
+        from .ginet_finetune_mp import GINet
+        if self.vocabulary is None:
+            self.load_motifs(self.dataset.get_data_loaders()[0])
+        if self.config.get('fp16_precision', False):
+            mcfg['precision'] = 'bf16'
+        plain = self._load_pre_trained_weights(PlainGINet(task, **mcfg).to(self.device))
+        rows, feats = self.embed_vocabulary(plain)
+        model = GINet(len(self.vocabulary), task, **mcfg).to(self.device)
+        model = self._load_pre_trained_weights(model)
+        init = model.motif_embedding.weight.detach().clone()
+        init[rows] = feats
+        model.init_motif_emb(init)
+        return model
 
     def build_optimizers(self, model):
         """finetune.py:167-178: parameters whose name contains 'pred_lin' at
@@ -190,14 +242,26 @@ class FineTune(object):
         return model
 
     # -- one batch ----------------------------------------------------------------
-    def _step(self, model, data):
+    def _to_device(self, data):
+        """(data on the device, the motif model's (mol_idx, clique_idx) or
+        None); the index tensors are built from the host copy of mol_index."""
+        motif = None
+        if self.config['model_type'] == 'gin_motif':
+            from .motifs import motif_batch
+            motif = motif_batch(data.mol_index, self.assignments, self.device)
+        return data.to(self.device), motif
+
+    def _step(self, model, data, motif=None):
         """(pred, loss) of a batch (finetune.py:89-102); the graph's status
         word -- which the head adds its label bit to -- joins the sticky word."""
         if self.task == 'classification':
             target = data.y.flatten()
         else:
             target = self.normalizer.norm(data.y) if self.normalizer else data.y
-        _, pred, loss = model.loss(data, target, self.criterion)
+        if motif is not None:
+            _, pred, loss = model.loss(data, *motif, target, self.criterion)
+        else:
+            _, pred, loss = model.loss(data, target, self.criterion)
         g = getattr(data, "_molclr_graph", None)
         if g is not None:
             torch.bitwise_or(self._status, g.status, out=self._status)
@@ -210,10 +274,10 @@ class FineTune(object):
         raise_for_status(int(self._status.item()))
 
     def train_step(self, model, optimizers, data):
-        data = data.to(self.device)
+        data, motif = self._to_device(data)
         for opt in optimizers:
             opt.zero_grad()
-        _, loss = self._step(model, data)
+        _, loss = self._step(model, data, motif)
         loss.backward()
         for opt in optimizers:
             opt.step()
@@ -224,7 +288,9 @@ class FineTune(object):
         if self.config.get('seed') is not None:
             torch.manual_seed(int(self.config['seed']))
             np.random.seed(int(self.config['seed']))
-        _, train_loader, valid_loader, test_loader = self.dataset.get_data_loaders()
+        smiles_data, train_loader, valid_loader, test_loader = self.dataset.get_data_loaders()
+        if self.config['model_type'] == 'gin_motif':
+            self.load_motifs(smiles_data)
 
         self.normalizer = None
         if self.config['task_name'] in ['qm7', 'qm9']:
@@ -280,8 +346,8 @@ class FineTune(object):
         with torch.no_grad():
             model.eval()
             for data in loader:
-                data = data.to(self.device)
-                pred, loss = self._step(model, data)
+                data, motif = self._to_device(data)
+                pred, loss = self._step(model, data, motif)
                 total += loss.item() * data.y.size(0)
                 num_data += data.y.size(0)
                 if self.normalizer:

@@ -1571,3 +1571,124 @@ def task_head(x, weights, biases, acts, loss=None, target=None, status=None):
     if not task_head_fused([x.shape[1]] + [W.shape[0] for W in weights]):
         return _task_head_composed(x, weights, biases, acts, loss_code, target, status)
     return _TaskHead.apply(x, target, status, loss_code, acts, *weights, *biases)
+
+
+# ---------------------------------------------------------------------------
+# Motif readout (motif_pool.hip): the attention pool of the motif model
+# ---------------------------------------------------------------------------
+MOTIF_POOL = os.environ.get("MOLCLR_MOTIF_POOL", "1") != "0"
+
+
+class _MotifPool(torch.autograd.Function):
+    """molclr_motif_pool_fwd / _bwd: a [B, F] in one launch, the backward in
+    two after a stable sort of the items by motif id."""
+
+    @staticmethod
+    def forward(ctx, h, E, clique_idx, mol_ptr, w, c, status):
+        hc, Ec, wc, cc = _c(h), _c(E), _c(w), _c(c)
+        B, F = hc.shape
+        T = clique_idx.shape[0]
+        dev = hc.device
+        a = torch.empty(B, F, dtype=torch.float32, device=dev)
+        alpha = torch.empty(T + B, dtype=torch.float32, device=dev)
+        _lib.call("molclr_motif_pool_fwd", hc.data_ptr(), Ec.data_ptr(), clique_idx.data_ptr(),
+                  mol_ptr.data_ptr(), wc.data_ptr(), cc.data_ptr(), B, T, F, Ec.shape[0],
+                  a.data_ptr(), alpha.data_ptr(), _lib.ptr(status), _stream(hc))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(hc, Ec, clique_idx, mol_ptr, wc, alpha, a)
+        ctx.params = (E, w, c)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        if da is None:
+            return (None,) * 7
+        h, E, clique_idx, mol_ptr, w, alpha, a = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        pE, pw, pc = ctx.params
+        B, F = h.shape
+        T = clique_idx.shape[0]
+        dev = h.device
+        da = _c(da)
+        dh = torch.empty_like(h) if need[0] else None
+        ebuf = wbuf = cbuf = rE = rw = rc = None
+        eacc = wacc = cacc = 0
+        sorted_idx = order = None
+        if need[1]:
+            ebuf, eacc, rE = _grad_sink(pE, E.shape, dev)
+            if T:  # the items grouped by motif id, ascending item order within one
+                sorted_idx, order = torch.sort(clique_idx, stable=True)
+        if need[4]:
+            wbuf, wacc, rw = _grad_sink(pw, pw.shape, dev)
+        if need[5]:
+            cbuf, cacc, rc = _grad_sink(pc, pc.shape, dev)
+        ws_bytes = _wsq("molclr_motif_pool_workspace_bytes", B, T, F)
+        ws = _ws(ws_bytes, dev)
+        _lib.call("molclr_motif_pool_bwd", da.data_ptr(), h.data_ptr(), E.data_ptr(),
+                  clique_idx.data_ptr(), mol_ptr.data_ptr(), _lib.ptr(sorted_idx), _lib.ptr(order),
+                  w.data_ptr(), a.data_ptr(), alpha.data_ptr(), B, T, F, E.shape[0], _lib.ptr(dh),
+                  _lib.ptr(ebuf), _lib.ptr(wbuf), _lib.ptr(cbuf), eacc, wacc, cacc, ws.data_ptr(),
+                  ws_bytes, _stream(h))
+        return dh, rE, None, None, rw, rc, None
+
+
+def _motif_pool_composed(h, E, clique_idx, mol_ptr, w, c, status):
+    """The same pool from torch ops (index_select, segment max and sum by
+    scatter_reduce, index_add), PyG's softmax with its 1e-16."""
+    B, F = h.shape
+    T, num = clique_idx.shape[0], E.shape[0]
+    dev = h.device
+    ptr = mol_ptr.to(torch.long)
+    bad_ptr = (ptr[1:] < ptr[:-1]).any() | (ptr[0] != 0) | (ptr[-1] != T)
+    bad = (clique_idx < 0) | (clique_idx >= num)  # never an index: clamped, its molecule NaN
+    item_mol = torch.searchsorted(ptr[1:].contiguous(), torch.arange(T, device=dev),
+                                  right=True).clamp_(max=B - 1)
+    seg = torch.cat([item_mol, torch.arange(B, device=dev)])
+    x = torch.cat([E.index_select(0, clique_idx.clamp(0, max(num - 1, 0))) if T else
+                   h.new_zeros(0, F), h], 0)
+    g = x @ w.reshape(F) + c.reshape(())
+    m = torch.full((B,), float("-inf"), device=dev).scatter_reduce(
+        0, seg, g, "amax", include_self=True)
+    e = torch.exp(g - m[seg])
+    s = torch.zeros(B, device=dev).index_add(0, seg, e)
+    alpha = e / (s[seg] + 1e-16)
+    a = torch.zeros(B, F, device=dev).index_add(0, seg, alpha[:, None] * x)
+    bad_mol = torch.zeros(B, device=dev).index_add(0, item_mol, bad.to(torch.float32)) > 0
+    bad_mol = bad_mol | bad_ptr
+    if status is not None:
+        status.bitwise_or_((bad_mol.any() * _lib.STATUS_MOTIF_RANGE).to(torch.int32))
+    return torch.where(bad_mol[:, None], torch.full_like(a, float("nan")), a)
+
+
+def motif_pool(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status=None):
+    """The motif model's attention pool (ginet_finetune_mp.py:158-160, PyG's
+    GlobalAttention with gate_nn = Linear(F, 1)): ``a [B, F]`` with ``a[b] =
+    sum_i alpha_i x_i`` over the rows ``E[clique_idx[i]]``, ``i`` in
+    ``[mol_ptr[b], mol_ptr[b + 1])``, then ``h[b]`` last, ``alpha`` the
+    softmax over the segment of ``x . gate_weight + gate_bias``.
+    ``clique_idx`` int64 [T], ``mol_ptr`` [B + 1] (0 = p_0 <= ... <= p_B = T).
+    A motif index outside E's rows, or a ``mol_ptr`` that breaks that rule,
+    sets STATUS_MOTIF_RANGE in ``status`` (an int32 device word) and makes
+    that molecule's row NaN; nothing here synchronises.  MOLCLR_MOTIF_POOL=0
+    composes the pool from torch ops instead of the fused kernels."""
+    _check(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status)
+    if h.dim() != 2 or E.dim() != 2 or E.shape[1] != h.shape[1]:
+        raise ValueError(f"motif_pool: h {tuple(h.shape)} and E {tuple(E.shape)} must be "
+                         "[B, F] and [num_motifs, F]")
+    B, F = h.shape
+    if B < 1:
+        raise ValueError("motif_pool: at least one molecule")
+    if clique_idx.dim() != 1 or clique_idx.dtype != torch.long:
+        raise ValueError("motif_pool: clique_idx must be int64 [T]")
+    if mol_ptr.dim() != 1 or mol_ptr.shape[0] != B + 1 or mol_ptr.dtype not in (torch.int32,
+                                                                              torch.long):
+        raise ValueError(f"motif_pool: mol_ptr must be an integer [B + 1] = [{B + 1}], got "
+                         f"{mol_ptr.dtype} {tuple(mol_ptr.shape)}")
+    if gate_weight.numel() != F or gate_bias.numel() != 1:
+        raise ValueError("motif_pool: gate_weight must hold F values and gate_bias one")
+    if h.dtype != torch.float32 or E.dtype != torch.float32:
+        raise ValueError("motif_pool: h and E must be float32")
+    clique_idx, mol_ptr = _c(clique_idx), _c(mol_ptr.to(torch.int32))
+    if not MOTIF_POOL:
+        return _motif_pool_composed(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status)
+    return _MotifPool.apply(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status)
