@@ -1214,6 +1214,41 @@ int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
                           int acc_dweight, int acc_dbias, void* workspace, size_t workspace_bytes,
                           molclr_stream_t stream);
 
+/* ---- Captured fine-tuning step (molclr_amd/finetune_step.py) -----------------
+ * The fine-tuning loops (finetune.py:89-102 a training batch, finetune.py:259-317
+ * an evaluation pass) replayed from HIP graphs over one staged segment.
+ *   molclr_stage_task (outside the captured region; one launch):
+ *     molclr_stage_segments of ONE segment -- same buffers, same refusals --
+ *     that also copies the batch's targets to target_dst, the fixed buffer the
+ *     graph's task head reads: int64 labels [target_rows] (target_is_float 0,
+ *     target_cols 1) or fp32 values [target_rows, target_cols].  target_rows
+ *     must be dst->num_graphs.
+ *   molclr_task_step_tail (the training graph's closing launch): advances the
+ *     step counters of up to two Adam optimizers (either may be NULL; GCN has
+ *     a base and a pred_lin group), copies the loss scalar and ORs the batch's
+ *     status word into the sticky word, as molclr_step_tail.
+ *   molclr_eval_tail (the evaluation graph's closing launch; one workgroup):
+ *     with n = *cursor, copies pred [B, C] to pred_all[n : n + B] and the
+ *     staged targets (target_row_words 4-byte words per row: 2 for int64
+ *     labels, C for fp32 values) to target_all[n : n + B], adds
+ *     (double)*loss * B to *loss_acc, ORs *status_src (nullable) into
+ *     *status_acc and sets *cursor = n + B.  If n + B > capacity (rows of
+ *     pred_all / target_all) nothing is stored, the cursor and the sum stay,
+ *     and MOLCLR_STATUS_EVAL_OVERFLOW is set in *status_acc. */
+#define MOLCLR_STATUS_EVAL_OVERFLOW 64 /* status bit: evaluation rows past the capacity */
+int molclr_stage_task(const molclr_stage_source* src, const molclr_graph_staged_segment* dst,
+                      int64_t* x_all, int64_t num_nodes_cap, int64_t num_edges_cap,
+                      int64_t* counts, const void* target_src, void* target_dst,
+                      int64_t target_rows, int64_t target_cols, int target_is_float,
+                      molclr_stream_t stream);
+int molclr_task_step_tail(int32_t* step_a, int32_t* step_b, const float* loss_src,
+                          float* loss_dst, const int32_t* status_src, int32_t* status_acc,
+                          molclr_stream_t stream);
+int molclr_eval_tail(const float* pred, const void* target, int64_t B, int64_t C,
+                     int64_t target_row_words, const float* loss, float* pred_all,
+                     void* target_all, int64_t capacity, int64_t* cursor, double* loss_acc,
+                     const int32_t* status_src, int32_t* status_acc, molclr_stream_t stream);
+
 /* ---- Benchmark instrumentation (no reference counterpart) -------------------
  * Opt-in kernel timer.  While a kind is enabled, its launches go through
  * hipExtLaunchKernelGGL with a start/stop event pair recorded by the dispatch

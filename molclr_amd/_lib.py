@@ -196,6 +196,9 @@ SIGNATURES = {
                                       _P]),
     "molclr_motif_pool_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64,
                                       _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "molclr_stage_task": (c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, c_int, _P]),
+    "molclr_task_step_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "molclr_eval_tail": (c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "molclr_ktimer_start": (c_int, [c_int]),
     "molclr_ktimer_read": (c_int, [c_int, _P, _P]),
     "molclr_ktimer_stop": (c_int, []),
@@ -210,6 +213,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 STATUS_ATOM_RANGE = 8  # MOLCLR_STATUS_ATOM_RANGE
 STATUS_LABEL_RANGE = 16  # MOLCLR_STATUS_LABEL_RANGE
 STATUS_MOTIF_RANGE = 32  # MOLCLR_STATUS_MOTIF_RANGE
+STATUS_EVAL_OVERFLOW = 64  # MOLCLR_STATUS_EVAL_OVERFLOW
 TASK_HEAD_MAX_LAYERS = 10
 TASK_HEAD_MAX_CLASSES = 16
 TASK_HEAD_MAX_DIM = 2044

@@ -12,6 +12,7 @@
 // Slots are claimed with integer atomics and each (short) row is then sorted by
 // edge id, so the result is deterministic.
 #include "common.h"
+#include "stage.h"
 
 namespace {
 
@@ -418,79 +419,16 @@ MOLCLR_API int molclr_graph_build(const int64_t* edge_index, const int64_t* edge
 // the real counts on the device, so one launch sequence serves every batch
 // whose sizes fit the capacities.
 // ---------------------------------------------------------------------------
-namespace {
-
-constexpr int kStageJobs = 5 * MOLCLR_MAX_SEGMENTS + 1;
-struct StageJob {
-  const int64_t* src;  // NULL: fill with 0
-  int64_t* dst;
-  int64_t count;
-};
-struct StageJobs {
-  StageJob j[kStageJobs];
-  int64_t counts[2 * MOLCLR_MAX_SEGMENTS];
-  int64_t* counts_dst;
-  int ncounts;
-};
-
-// blockIdx.y: the job; grid-stride over its elements
-__global__ void k_stage(StageJobs jb) {
-  const StageJob& j = jb.j[blockIdx.y];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < j.count;
-       i += (int64_t)gridDim.x * blockDim.x)
-    j.dst[i] = j.src ? j.src[i] : 0;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < jb.ncounts)
-    jb.counts_dst[threadIdx.x] = jb.counts[threadIdx.x];
-}
-
-}  // namespace
-
 MOLCLR_API int molclr_stage_segments(int nseg, const molclr_stage_source* src,
                                      const molclr_graph_staged_segment* dst, int64_t* x_all,
                                      int64_t num_nodes_cap, int64_t num_edges_cap,
                                      int64_t* counts, molclr_stream_t stream) {
-  MOLCLR_REQUIRE(nseg >= 1 && nseg <= MOLCLR_MAX_SEGMENTS && src && dst && x_all && counts,
-                 "stage_segments: %d segments (1..%d) / null pointer", nseg, MOLCLR_MAX_SEGMENTS);
-  StageJobs jb{};
+  molclr::StageJobs jb{};
   int nj = 0;
-  int64_t row = 0, edges = 0, most = 1;
-  auto job = [&](const int64_t* from, int64_t* to, int64_t n) {
-    jb.j[nj++] = {from, to, n};
-    if (n > most) most = n;
-  };
-  for (int s = 0; s < nseg; ++s) {
-    const molclr_stage_source& a = src[s];
-    const molclr_graph_staged_segment& b = dst[s];
-    MOLCLR_REQUIRE(a.num_nodes >= 0 && a.num_edges >= 0 && a.num_nodes <= b.node_cap &&
-                       a.num_edges <= b.edge_cap,
-                   "stage_segments: segment %d has %lld nodes / %lld edges, capacity %lld / %lld", s,
-                   (long long)a.num_nodes, (long long)a.num_edges, (long long)b.node_cap,
-                   (long long)b.edge_cap);
-    MOLCLR_REQUIRE((a.num_nodes == 0 || (a.x && a.batch && b.batch)) &&
-                       (a.num_edges == 0 || (a.edge_index && a.edge_attr && b.edge_index &&
-                                             b.edge_attr)),
-                   "stage_segments: null buffer in segment %d", s);
-    job(a.x, x_all + 2 * row, 2 * a.num_nodes);
-    job(a.edge_index, const_cast<int64_t*>(b.edge_index), a.num_edges);
-    job(a.edge_index + a.num_edges, const_cast<int64_t*>(b.edge_index) + b.edge_cap, a.num_edges);
-    job(a.edge_attr, const_cast<int64_t*>(b.edge_attr), 2 * a.num_edges);
-    job(a.batch, const_cast<int64_t*>(b.batch), a.num_nodes);
-    jb.counts[s] = a.num_nodes;
-    jb.counts[nseg + s] = a.num_edges;
-    row += a.num_nodes;
-    edges += a.num_edges;
-  }
-  MOLCLR_REQUIRE(edges <= num_edges_cap, "stage_segments: %lld edges exceed the capacity %lld",
-                 (long long)edges, (long long)num_edges_cap);
-  MOLCLR_REQUIRE(row <= num_nodes_cap, "stage_segments: %lld nodes exceed the capacity %lld",
-                 (long long)row, (long long)num_nodes_cap);
-  job(nullptr, x_all + 2 * row, 2 * (num_nodes_cap - row));  // padding atoms: type 0, chirality 0
-  jb.counts_dst = counts;
-  jb.ncounts = 2 * nseg;
-  const int T = 256;
-  int64_t bx = molclr::ceil_div(most, T);
-  if (bx > 256) bx = 256;
-  hipLaunchKernelGGL(k_stage, dim3((unsigned)bx, nj), dim3(T), 0, molclr::as_stream(stream), jb);
+  int64_t most = 1;
+  MOLCLR_TRY_RC(molclr::stage_plan("stage_segments", nseg, src, dst, x_all, num_nodes_cap,
+                                   num_edges_cap, counts, jb, nj, most));
+  molclr::stage_launch(jb, nj, most, molclr::as_stream(stream));
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }

@@ -213,6 +213,8 @@ def raise_for_status(st: int) -> None:
             what.append("motif index outside the motif embedding table, or molecule "
                         "segments of the motif items not ascending "
                         "(the reference's nn.Embedding raises IndexError)")
+        if st & _lib.STATUS_EVAL_OVERFLOW:
+            what.append("more evaluation rows than the gather buffers' capacity")
         raise ValueError("invalid graph batch: " + ", ".join(what))
 
 

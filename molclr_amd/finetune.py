@@ -19,9 +19,12 @@ the plain model embeds the motif vocabulary, then ginet_finetune_mp.GINet is
 built, loaded and given those rows as its motif table.  The motifs come from
 the optional key ``motifs``: ``builtin`` (molclr_amd.motifs' fragmenter, no
 RDKit, parity unpinned; the default) or the path of a JSON export of the
-reference's BRICS cliques.  Optional keys ``log_root``, ``ckpt_root`` and
-``seed``.  Invalid inputs (graph indices, atom features, class labels, motif
-indices) raise at the next log step (``check_inputs``), as in
+reference's BRICS cliques.  Optional keys ``log_root``, ``ckpt_root``,
+``seed`` and ``hip_graph`` (default False): with ``hip_graph: True`` the
+training step and the evaluation passes are replayed from HIP graphs
+(molclr_amd.finetune_step); a model those cannot take trains eagerly after
+one RuntimeWarning.  Invalid inputs (graph indices, atom features, class
+labels, motif indices) raise at the next log step (``check_inputs``), as in
 molclr_amd.molclr.
 """
 from __future__ import annotations
@@ -140,6 +143,10 @@ class FineTune(object):
         self.vocabulary = self.assignments = None  # model_type: gin_motif (load_motifs)
         # sticky OR of every step's graph + head status word (check_inputs)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # hip_graph: the captured step objects of the model being trained
+        # (_captured_for); None while the loop runs eagerly
+        self.hip_graph = bool(config.get('hip_graph', False))
+        self._captured = None
 
     def _get_device(self):
         if not torch.cuda.is_available() or self.config.get('gpu', 'cuda:0') == 'cpu':
@@ -271,9 +278,43 @@ class FineTune(object):
         """Raise if any batch so far had invalid inputs (a sync: called at the
         log steps and once per evaluation)."""
         from .data import raise_for_status
-        raise_for_status(int(self._status.item()))
+        st = int(self._status.item())
+        if self._captured is not None:  # the step objects' sticky words
+            step, ev = self._captured[2], self._captured[3]
+            if step is not None and step._made:
+                st |= int(step.status.item())
+            st |= ev._sticky
+        raise_for_status(st)
+
+    # -- hip_graph: True ----------------------------------------------------------
+    def _captured_for(self, model, optimizers=None):
+        """(step, eval) objects replaying ``model``'s train step and evaluation
+        from HIP graphs, or None: hip_graph is off, or the captured steps
+        cannot take the model (one RuntimeWarning naming the reason)."""
+        if not self.hip_graph:
+            return None
+        c = self._captured
+        if c is None or c[0] is not model:
+            from .finetune_step import CapturedEval, unsupported_reason
+            reason = unsupported_reason(model)
+            if reason is not None:
+                warnings.warn(f"hip_graph: True -- {reason}; fine-tuning runs eagerly",
+                              RuntimeWarning, stacklevel=3)
+                self.hip_graph = False
+                return None
+            c = self._captured = [model, None, None,
+                                  CapturedEval(model, self.criterion, self.normalizer)]
+        if optimizers is not None and (c[2] is None or c[1] is not optimizers):
+            from .finetune_step import CapturedFinetuneStep
+            c[1] = optimizers
+            c[2] = CapturedFinetuneStep(model, optimizers, self.criterion, self.normalizer)
+        return c[2], c[3]
 
     def train_step(self, model, optimizers, data):
+        captured = self._captured_for(model, optimizers)
+        if captured is not None:
+            # the step's loss is its own buffer, overwritten by the next replay
+            return captured[0].step(data.to(self.device)).clone()
         data, motif = self._to_device(data)
         for opt in optimizers:
             opt.zero_grad()
@@ -341,6 +382,24 @@ class FineTune(object):
         """(mean loss, metric) over a loader under no_grad / eval()
         (finetune.py:259-317): ROC-AUC of the class-1 logit, or MAE / RMSE of
         the de-normalised prediction."""
+        captured = self._captured_for(model)
+        if captured is not None:
+            total, predictions, labels = captured[1].run(loader)
+            model.train()
+            self.check_inputs()
+        else:
+            total, predictions, labels = self._evaluate_eager(model, loader)
+        if self.task == 'classification':
+            metric, name = roc_auc_score(labels, predictions[:, 1]), 'ROC AUC'
+        elif self.config['task_name'] in MAE_TASKS:
+            metric, name = mae_score(labels, predictions), 'MAE'
+        else:
+            metric, name = rmse_score(labels, predictions), 'RMSE'
+        print(f'{what} loss:', total, f'{name}:', metric)
+        return total, metric
+
+    def _evaluate_eager(self, model, loader):
+        """(mean loss, predictions, labels) of the launch-by-launch pass."""
         predictions, labels = [], []
         total, num_data = 0.0, 0
         with torch.no_grad():
@@ -357,15 +416,7 @@ class FineTune(object):
             self.check_inputs()
         model.train()
         total /= max(num_data, 1)
-        predictions, labels = np.concatenate(predictions), np.concatenate(labels)
-        if self.task == 'classification':
-            metric, name = roc_auc_score(labels, predictions[:, 1]), 'ROC AUC'
-        elif self.config['task_name'] in MAE_TASKS:
-            metric, name = mae_score(labels, predictions), 'MAE'
-        else:
-            metric, name = rmse_score(labels, predictions), 'RMSE'
-        print(f'{what} loss:', total, f'{name}:', metric)
-        return total, metric
+        return total, np.concatenate(predictions), np.concatenate(labels)
 
     def _test(self, model, test_loader):
         model_path = os.path.join(self.log_dir, 'checkpoints', 'model.pth')

@@ -1,0 +1,492 @@
+"""The fine-tuning train and evaluation steps captured as HIP graphs.
+
+The reference's fine-tuning loop (finetune.py:89-102 per training batch,
+finetune.py:259-317 per evaluation pass) enqueues ~105 launches for a batch of
+32 molecules whose kernels are nearly empty grids: the step is bound by the
+host.  As molclr_amd.graph_step does for pre-training, this module captures
+the step once per capacity bucket and replays it; the host cost per batch is
+one staging launch (``molclr_stage_task``: the batch and its targets into
+fixed buffers) and one graph launch.
+
+* :class:`CapturedFinetuneStep` -- ``step(data) -> loss``: the graph build,
+  ``zero_grad`` of every optimizer, ``model.loss_staged``, the backward, every
+  FusedAdam update and one closing launch (``molclr_task_step_tail``).
+* :class:`CapturedEval` -- ``run(loader) -> (mean_loss, predictions,
+  labels)`` under ``eval()`` / ``no_grad``: every batch is staged and replayed,
+  the graph's closing launch (``molclr_eval_tail``) gathers predictions,
+  targets and the loss sum on the device, and the pass ends with ONE
+  synchronisation and ONE device-to-host copy.  Its graphs are its own:
+  eval-mode BatchNorm records other kernels than the training step's.
+
+Both reuse graph_step's machinery: StagedPairGraph with one segment, the
+device-sized graph build and BatchNorm, padding rows that carry no gradient, a
+dry run before and a private memory pool for every capture, and dropout keys
+drawn from a device counter so replays get fresh masks.  State that crosses
+replays lives outside the pools: parameters, moments, the loss / status /
+gather buffers, the staged targets and the task head's ticket word
+(ops.CAPTURE_HEAD_SYNC: one per step object, made before the capture -- the
+capture stream is not the stream the dry run ran on).
+
+Single process only: fine-tuning has no data-parallel path.  The motif model
+(ginet_finetune_mp) is not taken: its item count varies per batch and
+ops.motif_pool has no device-sized form.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes
+from collections import OrderedDict
+
+import torch
+
+from . import _lib, ops
+from .data import _num_graphs_of, raise_for_status
+from .graph_step import StagedPairGraph, _Captured, _round_up
+
+
+def unsupported_reason(model) -> str | None:
+    """Why the captured steps cannot take ``model`` (None: they can)."""
+    from .ginet_finetune import FinetuneReadout
+    from .ginet_finetune_mp import GINet as MotifGINet
+    if isinstance(model, MotifGINet):
+        return "the motif model's item count varies per batch (no device-sized motif_pool)"
+    if not isinstance(model, FinetuneReadout):
+        return "the model has no loss_staged"
+    if not model.use_executor or model.num_layer > 16:
+        return "the encoder executor is off"
+    if model._dim_pad():
+        return f"emb_dim {model.emb_dim} needs padding to the kernels' width"
+    lins, _ = model._head_layers()
+    dims = [model.emb_dim, model.feat_dim] + [m.out_features for m in lins]
+    if not ops.task_head_fused(dims):
+        return (f"a task head of widths {dims} is composed from separate launches "
+                f"(fused up to {_lib.TASK_HEAD_MAX_DIM})")
+    return None
+
+
+class StagedTaskGraph(StagedPairGraph):
+    """A one-segment StagedPairGraph with the batch's targets: ``target`` is
+    int64 [B] (class labels) or fp32 [B, C], written by ``stage_task``."""
+
+    def __init__(self, device, node_cap: int, edge_cap: int, graphs: int, labels: bool, cols: int):
+        super().__init__(device, node_cap, edge_cap, [graphs])
+        self.labels, self.cols = bool(labels), 1 if labels else int(cols)
+        if labels:
+            self.target = torch.zeros(graphs, dtype=torch.long, device=device)
+        else:
+            self.target = torch.zeros(graphs, self.cols, dtype=torch.float32, device=device)
+
+    def stage_task(self, data) -> None:
+        """The batch's x / edge_index / edge_attr / batch and ``data.y`` in, one
+        launch on the current stream; the inputs stay alive until the next."""
+        B = self.graphs_per_segment[0]
+        if _num_graphs_of(data) != B:
+            raise ValueError(f"StagedTaskGraph: {_num_graphs_of(data)} molecules, built for {B}")
+        if data.x.device.type != "cuda" or data.y.device.type != "cuda":
+            raise RuntimeError("StagedTaskGraph: the batch must be on the GPU")
+        x = data.x.to(torch.long).contiguous()
+        ei = data.edge_index.to(torch.long).contiguous()
+        ea = data.edge_attr.to(torch.long).contiguous()
+        b = getattr(data, "batch", None)
+        if b is None:
+            b = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
+        b = b.to(torch.long).contiguous()
+        if self.labels:
+            y = data.y.reshape(B).to(torch.long).contiguous()
+        else:
+            y = data.y.reshape(B, self.cols).to(torch.float32).contiguous()
+        src = _lib.StageSourceC(x.data_ptr(), ei.data_ptr(), ea.data_ptr(), b.data_ptr(),
+                                int(x.shape[0]), int(ei.shape[1]))
+        _lib.call("molclr_stage_task", ctypes.addressof(src), ctypes.addressof(self._dst),
+                  self.x.data_ptr(), self.num_nodes, self.num_edges, self.counts.data_ptr(),
+                  y.data_ptr(), self.target.data_ptr(), B, self.cols, int(not self.labels),
+                  _lib.stream_of(self.device))
+        self._keep = [x, ei, ea, b, y]
+
+
+class _CapturedTask:
+    """What the two step objects share: the buckets, their lookup and the
+    capture discipline of graph_step.CapturedTrainStep (dry run first, a
+    private pool per capture, CAPTURE_SCOPE / CAPTURE_KEEP, the plane
+    generation bumped before and after)."""
+
+    def __init__(self, model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
+                 node_slack, edge_headroom, device=None):
+        from .ginet_finetune import TASK_LOSS
+        if not hasattr(model, "loss_staged"):
+            raise TypeError(f"{type(self).__name__}: the model has no loss_staged")
+        self.model = model
+        self.criterion = criterion or TASK_LOSS[model.task]
+        if self.criterion not in ("cross_entropy", "mse", "l1"):
+            raise ValueError(f"criterion {criterion!r}: 'cross_entropy', 'mse' or 'l1'")
+        self.labels = self.criterion == "cross_entropy"
+        self.normalizer = None if self.labels else normalizer
+        self.node_quantum, self.edge_quantum = int(node_quantum), int(edge_quantum)
+        self.node_slack = 2 * self.node_quantum if node_slack is None else int(node_slack)
+        self.edge_headroom = float(edge_headroom)
+        self.max_graphs = int(max_graphs)
+        self._graphs: OrderedDict = OrderedDict()
+        self.captures = 0
+        self.replays = 0
+        self.last_graph: StagedTaskGraph | None = None
+        self.device = device
+        self._made = False
+
+    # -- device state, made on first use (the arithmetic above needs no GPU) ----
+    def _make_state(self) -> None:
+        if self._made:
+            return
+        if self.device is None:
+            self.device = next(self.model.parameters()).device
+        self.out_dim = int(self.model._head_layers()[0][-1].out_features)
+        self._head_sync = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._alloc()
+        self._made = True
+
+    def _alloc(self) -> None:
+        raise NotImplementedError
+
+    # -- buckets ---------------------------------------------------------------
+    @staticmethod
+    def _need(data) -> tuple:
+        """(nodes, edges, molecules) of a batch, or of a size tuple."""
+        if isinstance(data, tuple):
+            n, e, g = data
+            return int(n), int(e), int(g)
+        return int(data.x.shape[0]), int(data.edge_index.shape[1]), _num_graphs_of(data)
+
+    def bucket(self, data) -> tuple:
+        """(node_cap, edge_cap, molecules) a new capture for this batch gets."""
+        n, e, g = self._need(data)
+        e_cap = _round_up(int(e * (1.0 + self.edge_headroom)) + 1, self.edge_quantum)
+        return (_round_up(n, self.node_quantum), e_cap, g)
+
+    def pick(self, keys, data):
+        """Of the captured ``keys`` (node_cap, edge_cap, molecules), the one
+        this batch replays on: the smallest that holds it with the same
+        molecule count (a partial last batch is a bucket of its own) and a
+        node capacity within ``node_slack`` rows of the batch's own rounded
+        size; None when none does."""
+        n, e, g = self._need(data)
+        limit = _round_up(n, self.node_quantum) + self.node_slack
+        best = None
+        for k in keys:
+            if k[0] >= n and k[1] >= e and k[0] <= limit and k[2] == g:
+                if best is None or k[:2] < best[:2]:
+                    best = k
+        return best
+
+    def lookup(self, data):
+        """The captured entry this batch would replay on, or None."""
+        k = self.pick(list(self._graphs), data)
+        return None if k is None else self._graphs[k]
+
+    def _insert(self, key, ent) -> None:
+        self._graphs[key] = ent
+        if len(self._graphs) > self.max_graphs:
+            self._graphs.popitem(last=False)
+
+    def _entry(self, data):
+        self._make_state()
+        k = self.pick(list(self._graphs), data)
+        if k is None:
+            k = self.bucket(data)
+            self._insert(k, self._capture(k, data))  # stages this batch too
+            return self._graphs[k], True
+        self._graphs.move_to_end(k)  # least-recently-replayed eviction
+        return self._graphs[k], False
+
+    def prepare(self, batches) -> int:
+        """Capture (without running) every graph the given batches need;
+        returns the number of new captures."""
+        before = self.captures
+        with self._mode():
+            for data in batches:
+                self._entry(data.to(self.device) if self.device is not None else data)
+        return self.captures - before
+
+    def _mode(self):
+        """The context captures and replays run in."""
+        return contextlib.nullcontext()
+
+    @property
+    def buckets(self) -> list:
+        """(node_cap, edge_cap, molecules) of every live capture."""
+        return list(self._graphs)
+
+    # -- capture ---------------------------------------------------------------
+    def _optimizers(self) -> tuple:
+        return ()
+
+    def _body(self, graph):
+        """The step through the Python layer (the dry run and the capture run
+        the same code); returns what must stay alive until it is recorded."""
+        raise NotImplementedError
+
+    def _target(self, graph):
+        """The head's target: the staged one, normalised with the torch ops the
+        eager loop uses (FineTune._step) -- the same arithmetic by construction."""
+        return self.normalizer.norm(graph.target) if self.normalizer else graph.target
+
+    def _capture(self, key, data=None) -> _Captured:
+        reason = unsupported_reason(self.model)
+        if reason is None and not self.model._executor_ok():
+            reason = "the encoder executor does not take the model's BatchNorm / dropout settings"
+        if reason:
+            raise NotImplementedError(f"{type(self).__name__}: {reason}")
+        ops._check_no_timer()
+        graph = StagedTaskGraph(self.device, key[0], key[1], key[2], self.labels, self.out_dim)
+        if data is not None:
+            graph.stage_task(data)
+        for opt in self._optimizers():
+            opt.sync_lr()
+        # the capture must record the weight-plane regeneration: make every
+        # cached image stale so the forward's first lookup refreshes them all
+        ops.bump_param_generation()
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize(self.device)
+        ops.CAPTURE_HEAD_SYNC = self._head_sync
+        try:
+            # dry run: every library call skipped; what it leaves behind (the
+            # weight images, the dropout state) is what the capture must not
+            # allocate from its pool
+            with _lib.dry_run():
+                held = self._body(graph)
+            del held
+            ops.bump_param_generation()
+            torch.cuda.synchronize(self.device)
+            ops.CAPTURE_SCOPE = {id(p) for p in self.model.parameters()}
+            ops.CAPTURE_KEEP = keep = []
+            # a private pool per capture (graph_step.CapturedTrainStep)
+            with torch.cuda.graph(g, pool=torch.cuda.graph_pool_handle()):
+                graph.build()
+                held = self._body(graph)
+            del held
+        finally:
+            ops.CAPTURE_SCOPE = None
+            ops.CAPTURE_KEEP = None
+            ops.CAPTURE_HEAD_SYNC = None
+        self.captures += 1
+        # a capture only records: the cached images must be regenerated by the
+        # next eager use as well
+        ops.bump_param_generation()
+        return _Captured(graph, g, keep)
+
+    def _replay(self, data):
+        ent, fresh = self._entry(data)
+        if not fresh:
+            ent.graph.stage_task(data)
+            for opt in self._optimizers():
+                opt.sync_lr()
+        ent.cuda_graph.replay()
+        self.replays += 1
+        self.last_graph = ent.graph
+        return ent
+
+    def check(self) -> None:
+        """Raise ValueError if any replayed batch so far had invalid inputs."""
+        self._make_state()
+        raise_for_status(int(self.status.item()))
+
+    def close(self) -> None:
+        """Release every captured graph (and its pool's memory) now."""
+        if self.device is not None:
+            torch.cuda.synchronize(self.device)
+        self._graphs.clear()
+        self.last_graph = None
+        import gc
+        gc.collect()
+        if self.device is not None:
+            torch.cuda.synchronize(self.device)
+
+
+class CapturedFinetuneStep(_CapturedTask):
+    """``step(data) -> loss``: one fine-tuning step (finetune.py:89-102 with
+    the trainer's zero_grad / backward / Adam around it) replayed from a HIP
+    graph captured per capacity bucket; ``data`` is a labelled batch on the
+    GPU (``.y``: int64 class labels or float targets [B, C]).
+
+    ``optimizers``: one FusedAdam or two (GCN's base and ``pred_lin`` groups);
+    each keeps its own learning rate on the device, synced before every
+    replay.  ``criterion``: 'cross_entropy', 'mse', 'l1' or None (by the
+    model's task); ``normalizer`` (finetune.Normalizer) is applied to float
+    targets inside the graph.  Buckets are keyed (node capacity, edge
+    capacity, molecules): lookup as graph_step.CapturedTrainStep's, and a
+    partial last batch gets a bucket of its own.
+
+    The returned loss is this object's own buffer, overwritten by the next
+    step.  ``status`` ORs every replayed batch's validity word -- graph
+    indices, atom features and the head's class-label bit -- and ``check()``
+    raises for an invalid batch at any earlier step."""
+
+    def __init__(self, model, optimizers, criterion=None, normalizer=None, node_quantum: int = 256,
+                 edge_quantum: int = 2048, max_graphs: int = 16, node_slack: int | None = None,
+                 edge_headroom: float = 0.04):
+        from .optim import FusedAdam
+        if isinstance(optimizers, FusedAdam):
+            optimizers = [optimizers]
+        optimizers = list(optimizers)
+        if not 1 <= len(optimizers) <= 2 or not all(isinstance(o, FusedAdam) for o in optimizers):
+            raise TypeError("CapturedFinetuneStep needs one or two molclr_amd.optim.FusedAdam "
+                            "(learning rate and step counter on the device)")
+        super().__init__(model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
+                         node_slack, edge_headroom, optimizers[0].flat.device)
+        self.optimizers = optimizers
+
+    def _optimizers(self):
+        return self.optimizers
+
+    def _alloc(self) -> None:
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # d loss / d loss from a tensor made before any capture: no fill
+        # kernel in the graph for autograd's ones_like(loss)
+        self._one = torch.ones((), dtype=torch.float32, device=self.device)
+
+    def _body(self, graph):
+        opts = self.optimizers
+        for opt in opts:
+            opt.zero_grad()
+        _, pred, loss = self.model.loss_staged(graph, self._target(graph), self.criterion)
+        loss.backward(self._one)
+        for opt in opts:
+            opt.step(sync_lr=False, tick=False)
+        # one closing launch: both step counters, the loss into this object's
+        # buffer, the batch's validity bits into the sticky status word
+        _lib.call("molclr_task_step_tail", opts[0]._step_dev.data_ptr(),
+                  opts[1]._step_dev.data_ptr() if len(opts) > 1 else None, loss.data_ptr(),
+                  self.loss.data_ptr(), graph.status.data_ptr(), self.status.data_ptr(),
+                  _lib.stream_of(self.device))
+        return pred, loss
+
+    def step(self, data) -> torch.Tensor:
+        if not self.model.training:
+            raise RuntimeError("CapturedFinetuneStep: the model must be in training mode")
+        self._replay(data)
+        # the replay's Adam steps changed the weights behind Python's back
+        ops.bump_param_generation()
+        return self.loss
+
+    __call__ = step
+
+
+class CapturedEval(_CapturedTask):
+    """``run(loader) -> (mean_loss, predictions, labels)``: an evaluation pass
+    (finetune.py:259-317) with every batch replayed from a HIP graph.
+
+    Where the eager loop synchronises three times per batch (``loss.item()``
+    and two ``.cpu()`` copies), the graph's closing launch appends the batch's
+    predictions and staged targets to device buffers behind a device cursor
+    and adds ``loss * B`` to an fp64 sum in the loop's order; the pass ends
+    with one synchronisation and one device-to-host copy.  Predictions are
+    de-normalised after the copy.  ``predictions`` is float32 [n, C],
+    ``labels`` the flattened targets (int64 or float32), both numpy.
+
+    ``capacity``: rows the gather buffers hold.  None (the default) sizes them
+    by the loader and grows them when a larger one comes (the graphs are
+    captured again: they hold the buffers' addresses); a given capacity is
+    kept, and rows past it are refused on the device (no store; the status
+    bit STATUS_EVAL_OVERFLOW makes ``run`` raise)."""
+
+    _HEADER = 64  # bytes: cursor int64, loss sum fp64, status int32
+
+    def __init__(self, model, criterion=None, normalizer=None, capacity: int | None = None,
+                 node_quantum: int = 256, edge_quantum: int = 2048, max_graphs: int = 16,
+                 node_slack: int | None = None, edge_headroom: float = 0.04):
+        super().__init__(model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
+                         node_slack, edge_headroom)
+        self.fixed = capacity is not None
+        self.capacity = int(capacity) if self.fixed else 0
+        self._sticky = 0  # status bits of earlier passes (check())
+
+    @contextlib.contextmanager
+    def _mode(self):
+        self._make_state()
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            self.model.train(was_training)
+
+    def _alloc(self) -> None:
+        # the normalizer's constants on the host, once: run() copies nothing else
+        n = self.normalizer
+        self._denorm = None if n is None else (n.std.detach().cpu(), n.mean.detach().cpu())
+        self._alloc_rows(self.capacity if self.fixed else max(self.capacity, 1024))
+
+    def _alloc_rows(self, rows: int) -> None:
+        """One buffer, so that one copy brings everything to the host: header,
+        pred_all [rows, C] fp32, target_all [rows] int64 or [rows, C] fp32."""
+        self._graphs.clear()  # they hold the old buffers' addresses
+        self.capacity = int(rows)
+        C = self.out_dim
+        pred_bytes = (rows * C * 4 + 15) // 16 * 16
+        tgt_bytes = rows * (8 if self.labels else 4 * C)
+        self._buf = torch.zeros(self._HEADER + pred_bytes + tgt_bytes, dtype=torch.uint8,
+                                device=self.device)
+        self._layout = (self._HEADER, self._HEADER + pred_bytes)
+        self.cursor, self.loss_acc, self.status, self.pred_all, self.target_all = \
+            self._views(self._buf)
+
+    def _views(self, buf):
+        p0, t0 = self._layout
+        rows, C = self.capacity, self.out_dim
+        cursor = buf[0:8].view(torch.long)
+        loss_acc = buf[8:16].view(torch.float64)
+        status = buf[16:20].view(torch.int32)
+        pred = buf[p0:p0 + rows * C * 4].view(torch.float32).view(rows, C)
+        if self.labels:
+            tgt = buf[t0:t0 + rows * 8].view(torch.long)
+        else:
+            tgt = buf[t0:t0 + rows * C * 4].view(torch.float32).view(rows, C)
+        return cursor, loss_acc, status, pred, tgt
+
+    def _body(self, graph):
+        _, pred, loss = self.model.loss_staged(graph, self._target(graph), self.criterion)
+        B, C = graph.graphs_per_segment[0], self.out_dim
+        _lib.call("molclr_eval_tail", pred.data_ptr(), graph.target.data_ptr(), B, C,
+                  2 if self.labels else C, loss.data_ptr(), self.pred_all.data_ptr(),
+                  self.target_all.data_ptr(), self.capacity, self.cursor.data_ptr(),
+                  self.loss_acc.data_ptr(), graph.status.data_ptr(), self.status.data_ptr(),
+                  _lib.stream_of(self.device))
+        return pred, loss
+
+    @staticmethod
+    def _rows_of(loader):
+        for obj in (getattr(loader, "sampler", None), loader):
+            if isinstance(obj, (list, tuple)):
+                return sum(_num_graphs_of(d) for d in obj)
+        s = getattr(loader, "sampler", None)
+        return len(s) if s is not None and hasattr(s, "__len__") else None
+
+    def run(self, loader):
+        self._make_state()
+        if not self.fixed:
+            rows = self._rows_of(loader)
+            if rows is None:  # unknown length: read it once
+                loader = list(loader)
+                rows = self._rows_of(loader)
+            if rows > self.capacity:
+                self._alloc_rows(rows)
+        self._buf[:self._HEADER].zero_()
+        with self._mode():
+            for data in loader:
+                self._replay(data.to(self.device))
+        host = self._buf.cpu()  # the pass's one synchronisation and one copy
+        cursor, loss_acc, status, pred, tgt = self._views(host)
+        self._sticky |= int(status.item())
+        raise_for_status(self._sticky)
+        n = int(cursor.item())
+        pred, tgt = pred[:n], tgt[:n]
+        if self._denorm is not None:  # Normalizer.denorm, after the copy
+            pred = pred * self._denorm[0] + self._denorm[1]
+        mean_loss = float(loss_acc.item()) / max(n, 1)
+        return mean_loss, pred.numpy().copy(), tgt.reshape(-1).numpy().copy()
+
+    def check(self) -> None:
+        raise_for_status(self._sticky)
+
+
+__all__ = ["CapturedEval", "CapturedFinetuneStep", "StagedTaskGraph", "unsupported_reason"]

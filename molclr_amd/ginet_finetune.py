@@ -38,7 +38,9 @@ class FinetuneReadout:
         raise NotImplementedError
 
     def _task(self, data, loss=None, target=None):
-        h, graph = self._embed(data)
+        return self._head(*self._embed(data), loss, target)
+
+    def _head(self, h, graph, loss=None, target=None):
         h, W = self._pool(h, graph)
         lins, acts = self._head_layers()
         return ops.task_head(h, [W] + [m.weight for m in lins],
@@ -56,6 +58,17 @@ class FinetuneReadout:
         launch: ``criterion`` 'cross_entropy' (int64 labels), 'mse' or 'l1'
         (float targets [B, 1]); default by task (cross-entropy / MSE)."""
         return self._task(data, criterion or TASK_LOSS[self.task], target)
+
+    def loss_staged(self, graph, target, criterion=None):
+        """:meth:`loss` over a staged graph (molclr_amd.graph_step.StagedPairGraph
+        of one segment): the atoms are ``graph.x``, fixed-capacity buffers whose
+        padding rows lie outside every molecule and carry no gradient -- the
+        capturable form of the step (molclr_amd.finetune_step)."""
+        if not self._executor_ok() or self._dim_pad():
+            raise NotImplementedError("loss_staged needs the encoder executor at a width "
+                                      "the kernels take unpadded")
+        return self._head(self._run_encoder(graph.x, graph), graph,
+                          criterion or TASK_LOSS[self.task], target)
 
     def load_my_state_dict(self, state_dict):
         """Copy every entry whose name the model has (a shape mismatch raises

@@ -136,3 +136,7 @@ class GINet(FinetuneReadout, ginet_molclr.GINet):
         head's launch, for both tasks (the reference's regression branch calls
         ``model(data)`` without the motif arguments and cannot run)."""
         return self._task(data, mol_idx, clique_idx, criterion or TASK_LOSS[self.task], target)
+
+    def loss_staged(self, graph, target, criterion=None):
+        raise NotImplementedError("the motif model has no staged form: its item count varies "
+                                  "per batch and ops.motif_pool has no device-sized form")

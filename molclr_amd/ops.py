@@ -1404,11 +1404,18 @@ _HEAD_LOSSES = {None: _lib.LOSS_NONE, "none": _lib.LOSS_NONE,
                 "cross_entropy": _lib.LOSS_CROSS_ENTROPY, "mse": _lib.LOSS_MSE,
                 "l1": _lib.LOSS_L1}
 _HEAD_SYNC: dict = {}
+# While a step is dry-run and captured (molclr_amd.finetune_step): the step
+# object's own ticket word.  The capture stream is not the stream the dry run
+# ran on, and a word made inside the capture would live in the graph's pool;
+# this one is made before either and every replay of the graph uses it.
+CAPTURE_HEAD_SYNC: torch.Tensor | None = None
 
 
 def _head_sync(dev) -> torch.Tensor:
     """The forward's ticket word (molclr_task_head.sync): zero between calls,
     one per device and stream so overlapping calls never share it."""
+    if CAPTURE_HEAD_SYNC is not None:
+        return CAPTURE_HEAD_SYNC
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     t = _HEAD_SYNC.get(key)
     if t is None:

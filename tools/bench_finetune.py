@@ -12,6 +12,14 @@ back-to-back iterations between two device syncs, wall-clock per iteration;
 reported are the median over rounds and the spread (min .. max).  Kernel
 launches per iteration are counted with the torch profiler.
 
+The captured column (molclr_amd.finetune_step) alternates with the eager one
+in the same rounds: ``step_captured`` is CapturedFinetuneStep.step on the same
+model and optimizer after ``prepare`` (``captures_in_timed_region`` counts what was
+captured while timing: 0 when prepare covered every batch), and
+``eval_eager`` / ``eval_captured`` are one evaluation pass over the batches --
+the eager loop of FineTune._evaluate (loss.item() and two .cpu() per batch)
+against CapturedEval.run -- in microseconds per batch.
+
     python tools/bench_finetune.py [--rounds 9] [--iters 50] [--out FILE]
 prints one JSON line per configuration.
 """
@@ -29,6 +37,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from molclr_amd import ops  # noqa: E402
 from molclr_amd.dataset import collate_views, random_molecule  # noqa: E402
+from molclr_amd.finetune_step import CapturedEval, CapturedFinetuneStep  # noqa: E402
 from molclr_amd.ginet_finetune import GINet  # noqa: E402
 from molclr_amd.optim import FusedAdam  # noqa: E402
 
@@ -38,8 +47,10 @@ def batches(B, n, dev, seed=0):
     out = []
     for _ in range(n):
         mols = [random_molecule(rng, "pubchem") for _ in range(B)]
-        b = collate_views([(m.x, m.edge_index, m.edge_attr) for m in mols]).to(dev)
-        out.append((b, torch.from_numpy(rng.integers(0, 2, B)).to(dev)))
+        b = collate_views([(m.x, m.edge_index, m.edge_attr) for m in mols])
+        b.y = torch.from_numpy(rng.integers(0, 2, (B, 1)))
+        b = b.to(dev)
+        out.append((b, b.y.flatten()))
     return out
 
 
@@ -91,8 +102,43 @@ def run(B, drop, rounds, iters, dev):
         pooled.grad = None
         ops.task_head(pooled, Ws, bs, [None] + acts, "cross_entropy", y0)[2].backward()
 
-    res = {"batch": B, "drop_ratio": drop, "rounds": rounds, "iters": iters}
+    # the captured column: the same model and optimizer (a second model's
+    # weight images would be regenerated with this one's after every step)
+    cstep = CapturedFinetuneStep(model, opt, "cross_entropy")
+    ceval = CapturedEval(model, "cross_entropy")
+    loader = [b for b, _ in data]
+    cstep.prepare(loader)
+    ceval.prepare(loader)
+
+    def step_captured(i):
+        cstep.step(loader[i % len(loader)])
+
+    def eval_eager(i):  # the body of FineTune._evaluate
+        total, preds, labels = 0.0, [], []
+        with torch.no_grad():
+            model.eval()
+            for b, y in data:
+                _, pred, loss = model.loss(b, y)
+                total += loss.item() * b.y.size(0)
+                preds.append(pred.cpu().numpy())
+                labels.append(b.y.cpu().flatten().numpy())
+        model.train()
+        return total, np.concatenate(preds), np.concatenate(labels)
+
+    def eval_captured(i):
+        return ceval.run(loader)
+
+    passes = max(1, iters // len(loader))
+    res = {"batch": B, "drop_ratio": drop, "rounds": rounds, "iters": iters,
+           "eval_batches": len(loader), "eval_passes_per_round": passes}
     times = {(w, f): [] for w in ("step", "head") for f in (1, 0)}
+    times.update({k: [] for k in (("step", "captured"), ("eval", "eager"), ("eval", "captured"))})
+    timed(step_captured, 10)
+    eval_eager(0)
+    eval_captured(0)
+    res["launches_step_captured"] = launches(step_captured)
+    res["buckets_step"] = cstep.buckets
+    captures_before = cstep.captures + ceval.captures
     for fused in (1, 0):
         ops.TASK_HEAD = bool(fused)
         timed(step, 10)
@@ -104,9 +150,16 @@ def run(B, drop, rounds, iters, dev):
             ops.TASK_HEAD = bool(fused)
             times[("step", fused)].append(timed(step, iters))
             times[("head", fused)].append(timed(head, iters))
+            if fused:  # the captured step and the evaluation passes, same rounds
+                times[("step", "captured")].append(timed(step_captured, iters))
+                times[("eval", "eager")].append(timed(eval_eager, passes) / len(loader))
+                times[("eval", "captured")].append(timed(eval_captured, passes) / len(loader))
     ops.TASK_HEAD = True
+    res["captures_in_timed_region"] = cstep.captures + ceval.captures - captures_before
     for (w, f), xs in times.items():
-        res[f"{w}_fused{f}"] = summary(xs)
+        res[f"{w}_fused{f}" if f in (0, 1) else f"{w}_{f}"] = summary(xs)
+    cstep.close()
+    ceval.close()
     return res
 
 
