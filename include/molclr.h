@@ -335,6 +335,17 @@ int molclr_gine_aggregate_bwd(const float* g, const int32_t* rowptr_t, const int
                               const uint32_t* nbr_t, const int32_t* ecount, float* dx, float* dE1, float* dE2,
                               int64_t num_nodes, int64_t dim, int accumulate, void* workspace,
                               size_t workspace_bytes, molclr_stream_t stream);
+/* molclr_gine_aggregate_bwd with the kernels chosen per call (tests and
+ * benchmarks): 0 = the transposed gather, then the edge-table partials (two
+ * passes over g); 1 = both in one pass over g when dx and a table gradient are
+ * asked for and num_nodes > 0 (otherwise as 0); -1 = automatic, as the call
+ * above: 1 unless the environment has MOLCLR_AGG_BWD_FUSED=0 (read once).
+ * The results of 0 and 1 are bit-identical. */
+int molclr_gine_aggregate_bwd_impl(const float* g, const int32_t* rowptr_t, const int32_t* col_t,
+                                   const uint32_t* nbr_t, const int32_t* ecount, float* dx,
+                                   float* dE1, float* dE2, int64_t num_nodes, int64_t dim,
+                                   int accumulate, void* workspace, size_t workspace_bytes,
+                                   molclr_stream_t stream, int impl);
 
 /* GCN aggregation (gcn_molclr.py:72-88; gcn_norm at :74 is computed and
  * discarded by the reference, so it is not computed here):

@@ -60,6 +60,8 @@ SIGNATURES = {
     "molclr_gine_aggregate_bwd_workspace_bytes": (c_size_t, [_I64, _I64]),
     "molclr_gine_aggregate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int, _P,
                                           c_size_t, _P]),
+    "molclr_gine_aggregate_bwd_impl": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int,
+                                               _P, c_size_t, _P, c_int]),
     "molclr_gcn_aggregate_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     "molclr_gcn_aggregate_bwd_workspace_bytes": (c_size_t, [_I64, _I64]),
     "molclr_gcn_aggregate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int,

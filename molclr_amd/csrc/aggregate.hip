@@ -599,6 +599,122 @@ __global__ void k_ecount_weighted_partial(const typename St::T* __restrict__ g,
   }
 }
 
+// k_transpose_gather and k_ecount_weighted_partial in one pass over g.  The
+// partial kernel already holds g[i][c], the self term of dx[i][c], in a
+// register; this kernel keeps its grid, partition plan, loop and LDS fold and
+// also gathers the row's out-neighbours and stores dx, so g is read from
+// memory once (the neighbour rows come from cache) and one launch goes.
+//   - first wave of loads, per row of the trip: the row's nbr_t slot, its two
+//     ecount words and g[i][c];
+//   - second wave: the neighbour elements of all U rows (slot rows; absent
+//     slots load nothing), issued before any add;
+//   - dx[i][c] by k_transpose_gather's additions in its order (zero, the
+//     neighbours in slot order or the CSC walk past MOLCLR_NBR_SLOTS, the self
+//     element last), then the ecount-weighted sums from the same v[u] in row
+//     order: dx and the partials are bit-identical to the two kernels'.
+// Rows: partition p owns [p rpp, min((p+1) rpp, N)) and P rpp >= N
+// (rpp = ceil(N / P)), thread (r, c) of it the rows beg + r + k band, so every
+// (row, column unit) of [0, N) is stored exactly once; rows at or past `end`
+// load the partition's first row's words and neither gather nor store.
+// U = kGatherRows = 2 rows a trip, not the partial kernel's eight: a row keeps
+// 1 + MOLCLR_NBR_SLOTS float4 in flight, and the c2 grid is 4096 waves, four a
+// SIMD, so the kernel is fastest where all of them are resident (<= 128
+// registers).  Measured at the c2 paired shape, call incl. the 6 us reduction:
+// U = 8 256 registers 56 us, 4 179 38 us, 3 145 36 us, 2 113 32 us, 1 80 32 us;
+// the two kernels 36 us.  Loading the next trip's slots a trip ahead: no gain.
+constexpr int kGatherRows = 2;
+template <typename St = StF32>
+__global__ __launch_bounds__(1024) void k_gather_ecount(
+    const typename St::T* __restrict__ g, const int32_t* __restrict__ rowptr_t,
+    const int32_t* __restrict__ col_t, const uint4* __restrict__ nbr_t,
+    const int32_t* __restrict__ ecount, typename St::T* __restrict__ dx, int64_t N, int d4,
+    int band, int64_t rows_per_part, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) float4 red[];  // [band][8][d4]
+  const int tid = threadIdx.x;
+  const bool live = tid < band * d4;
+  const int r = live ? tid / d4 : 0, c = live ? tid - r * d4 : 0;
+  const int64_t beg = (int64_t)blockIdx.x * rows_per_part;
+  int64_t end = beg + rows_per_part;
+  if (end > N) end = N;
+  float4 acc[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) acc[s] = f4zero();
+  if (live) {
+    constexpr int U = kGatherRows;
+    for (int64_t i0 = beg + r; i0 < end; i0 += U * (int64_t)band) {
+      uint4 sl[U];
+      int4 lo[U], hi[U];
+      float4 v[U], nb[U][MOLCLR_NBR_SLOTS];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + (int64_t)u * band;
+        const int64_t ii = i < end ? i : beg;
+        const int4* ec = reinterpret_cast<const int4*>(ecount + ii * 8);
+        sl[u] = nbr_t[ii];
+        lo[u] = ec[0];
+        hi[u] = ec[1];
+        v[u] = St::ld(g, ii * d4 + c);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint32_t w[MOLCLR_NBR_SLOTS] = {sl[u].x, sl[u].y, sl[u].z, sl[u].w};
+        // a row past `end` and a row of the CSC walk take no slot loads
+        uint32_t deg = i0 + (int64_t)u * band < end ? nbr_degree(sl[u].x) : 0;
+        if (deg > MOLCLR_NBR_SLOTS) deg = 0;
+#pragma unroll
+        for (int k = 0; k < MOLCLR_NBR_SLOTS; ++k)
+          nb[u][k] = deg > (uint32_t)k ? St::ld(g, (int64_t)nbr_node(w[k]) * d4 + c) : f4zero();
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + (int64_t)u * band;
+        if (i >= end) break;
+        const uint32_t deg = nbr_degree(sl[u].x);
+        float4 a = f4zero();
+        if (deg <= MOLCLR_NBR_SLOTS) {
+#pragma unroll
+          for (int k = 0; k < MOLCLR_NBR_SLOTS; ++k)
+            if (deg > (uint32_t)k) a = f4add(a, nb[u][k]);
+        } else {
+          for (int32_t k = rowptr_t[i], e = rowptr_t[i + 1]; k < e; ++k)
+            a = f4add(a, St::ld(g, (int64_t)col_t[k] * d4 + c));
+        }
+        St::st(dx, i * d4 + c, f4add(a, v[u]));
+        const int cnt[8] = {lo[u].x, lo[u].y, lo[u].z, lo[u].w, hi[u].x, hi[u].y, hi[u].z, hi[u].w};
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          const float w = (float)cnt[s];
+          acc[s].x += w * v[u].x;
+          acc[s].y += w * v[u].y;
+          acc[s].z += w * v[u].z;
+          acc[s].w += w * v[u].w;
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) red[(r * 8 + s) * d4 + c] = acc[s];
+  }
+  __syncthreads();
+  if (!live || r != 0) return;
+  double* out = partial + (int64_t)blockIdx.x * 8 * (4 * d4);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    double x = 0.0, y = 0.0, z = 0.0, w = 0.0;
+    for (int q = 0; q < band; ++q) {
+      const float4 v = red[(q * 8 + s) * d4 + c];
+      x += v.x;
+      y += v.y;
+      z += v.z;
+      w += v.w;
+    }
+    double* o = out + s * 4 * d4 + 4 * c;
+    o[0] = x;
+    o[1] = y;
+    o[2] = z;
+    o[3] = w;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // GCN aggregation (scalar edge embedding, bias)
 // ---------------------------------------------------------------------------
@@ -1035,15 +1151,43 @@ MOLCLR_API size_t molclr_gine_aggregate_bwd_workspace_bytes(int64_t N, int64_t D
   return (size_t)ecount_parts(N, molclr::make_band(D).band) * 8 * D * sizeof(double) + 256;
 }
 
-MOLCLR_API int molclr_gine_aggregate_bwd(const float* g, const int32_t* rowptr_t,
-                                         const int32_t* col_t, const uint32_t* nbr_t,
-                                         const int32_t* ecount, float* dx,
-                                         float* dE1, float* dE2, int64_t N, int64_t D,
-                                         int accumulate, void* workspace, size_t workspace_bytes,
-                                         molclr_stream_t stream) {
+// dx and the edge-table partials in one pass (default) or by the two kernels
+// (MOLCLR_AGG_BWD_FUSED=0, an A/B switch)
+static bool agg_bwd_fused() {
+  static const bool on = [] {
+    const char* e = getenv("MOLCLR_AGG_BWD_FUSED");
+    return !(e != nullptr && e[0] == '0');
+  }();
+  return on;
+}
+
+MOLCLR_API int molclr_gine_aggregate_bwd_impl(const float* g, const int32_t* rowptr_t,
+                                              const int32_t* col_t, const uint32_t* nbr_t,
+                                              const int32_t* ecount, float* dx, float* dE1,
+                                              float* dE2, int64_t N, int64_t D, int accumulate,
+                                              void* workspace, size_t workspace_bytes,
+                                              molclr_stream_t stream, int impl) {
   MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bwd: dim must be a multiple of 4");
+  MOLCLR_REQUIRE(impl >= -1 && impl <= 1, "gine_aggregate_bwd: impl %d (-1, 0 or 1)", impl);
   hipStream_t s = molclr::as_stream(stream);
   int d4 = (int)(D / 4);
+  const bool fusable = dx && (dE1 || dE2) && N > 0;
+  if (fusable && (impl < 0 ? agg_bwd_fused() : impl == 1)) {
+    MOLCLR_REQUIRE(g && rowptr_t && nbr_t && ecount, "gine_aggregate_bwd: null pointer");
+    MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gine_aggregate_bwd_workspace_bytes(N, D));
+    const molclr::Band b = molclr::make_band(D);
+    const int64_t P = ecount_parts(N, b.band);
+    const int64_t rpp = molclr::ceil_div(N, P);
+    double* partial = (double*)workspace;
+    const size_t lds = (size_t)b.band * 8 * b.d4 * sizeof(float4);
+    MOLCLR_REQUIRE(lds <= 65536, "gine_aggregate_bwd: dim too large for the edge-table reduction");
+    hipLaunchKernelGGL(k_gather_ecount<StF32>, dim3(P), dim3(b.threads), lds, s, g, rowptr_t, col_t,
+                       (const uint4*)nbr_t, ecount, dx, N, d4, b.band, rpp, partial);
+    hipLaunchKernelGGL(k_reduce_partials_split, dim3(molclr::ceil_div(8 * D, 16)), dim3(1024), 0, s,
+                       partial, P, (int64_t)8, D, (int64_t)5, dE1, dE2, accumulate);
+    MOLCLR_LAUNCHED();
+    return MOLCLR_OK;
+  }
   if (dx && N > 0) {
     MOLCLR_REQUIRE(g && rowptr_t && nbr_t, "gine_aggregate_bwd: null pointer");
     hipLaunchKernelGGL(k_transpose_gather<StF32>, dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0,
@@ -1064,6 +1208,16 @@ MOLCLR_API int molclr_gine_aggregate_bwd(const float* g, const int32_t* rowptr_t
   }
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
+}
+
+MOLCLR_API int molclr_gine_aggregate_bwd(const float* g, const int32_t* rowptr_t,
+                                         const int32_t* col_t, const uint32_t* nbr_t,
+                                         const int32_t* ecount, float* dx,
+                                         float* dE1, float* dE2, int64_t N, int64_t D,
+                                         int accumulate, void* workspace, size_t workspace_bytes,
+                                         molclr_stream_t stream) {
+  return molclr_gine_aggregate_bwd_impl(g, rowptr_t, col_t, nbr_t, ecount, dx, dE1, dE2, N, D,
+                                        accumulate, workspace, workspace_bytes, stream, -1);
 }
 
 MOLCLR_API int molclr_gcn_aggregate_fwd(const float* xw, const int32_t* rowptr,
