@@ -329,7 +329,10 @@ int molclr_gine_aggregate_bn_fwd(const float* z, const float* coeffs, int relu, 
                                  int64_t D, float* rowparts, float* slot, molclr_stream_t stream);
 /* Backward: dx[j] = Σ_{k in out(j), edge order} g[dst_k] + g[j];
  * dE1[t] = Σ_i ecount[i][t] g[i], dE2[d] = Σ_i ecount[i][5+d] g[i].
- * dx may be NULL (first layer input needs no grad); dE1/dE2 may be NULL. */
+ * dx may be NULL (first layer input needs no grad); dE1/dE2 may be NULL.
+ * dim must be a multiple of 4 in [4, 4096] (the edge-table reduction plans its
+ * blocks as molclr_colsum_f32 does): any other width is MOLCLR_ERR_ARG, and
+ * the workspace query returns 0 for it. */
 size_t molclr_gine_aggregate_bwd_workspace_bytes(int64_t num_nodes, int64_t dim);
 int molclr_gine_aggregate_bwd(const float* g, const int32_t* rowptr_t, const int32_t* col_t,
                               const uint32_t* nbr_t, const int32_t* ecount, float* dx, float* dE1, float* dE2,
@@ -569,7 +572,10 @@ int molclr_linear_wgrad_h3_pair(const float* dy_a, const float* dymax_a, const f
                                 int accumulate, void* workspace, size_t workspace_bytes,
                                 molclr_stream_t stream);
 
-/* out[n] = Σ_m X[m*ld + n]  (bias gradients), deterministic. */
+/* out[n] = Σ_m X[m*ld + n]  (bias gradients), deterministic.
+ * cols must be a multiple of 4 in [4, 4096] (one thread per float4 column, a
+ * block of at most 1024 threads holds a whole row) and ld a multiple of 4:
+ * any other width is MOLCLR_ERR_ARG, and its workspace query returns 0. */
 size_t molclr_colsum_f32_workspace_bytes(int64_t rows, int64_t cols);
 int molclr_colsum_f32(const float* X, float* out, int64_t rows, int64_t cols, int64_t ld,
                       int accumulate, void* workspace, size_t workspace_bytes,
@@ -585,7 +591,10 @@ int molclr_colsum_f32(const float* X, float* out, int64_t rows, int64_t cols, in
  * training == 0: running statistics are used and nothing is updated.
  * relu != 0 applies max(y, 0) to the output.  y may be NULL: the statistics
  * (save_mean / save_invstd, running stats) are computed and the normalised
- * output is not written. */
+ * output is not written.
+ * dim must be a multiple of 4 in [4, 4096] (the column-sum limit above), here
+ * and in every molclr_batchnorm_seg_* call below: any other width is
+ * MOLCLR_ERR_ARG, and its workspace query returns 0. */
 size_t molclr_batchnorm_workspace_bytes(int64_t rows, int64_t dim);
 int molclr_batchnorm_fwd(const float* z, const float* gamma, const float* beta,
                          float* running_mean, float* running_var,

@@ -1148,6 +1148,7 @@ MOLCLR_API int molclr_gine_aggregate_fwd_rowmax(const float* x, const int32_t* r
 }
 
 MOLCLR_API size_t molclr_gine_aggregate_bwd_workspace_bytes(int64_t N, int64_t D) {
+  if (!molclr::band_dim_ok(D)) return 0;  // refused by molclr_gine_aggregate_bwd
   return (size_t)ecount_parts(N, molclr::make_band(D).band) * 8 * D * sizeof(double) + 256;
 }
 
@@ -1167,7 +1168,9 @@ MOLCLR_API int molclr_gine_aggregate_bwd_impl(const float* g, const int32_t* row
                                               float* dE2, int64_t N, int64_t D, int accumulate,
                                               void* workspace, size_t workspace_bytes,
                                               molclr_stream_t stream, int impl) {
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bwd: dim must be a multiple of 4");
+  MOLCLR_REQUIRE(molclr::band_dim_ok(D),
+                 "gine_aggregate_bwd: dim %lld must be a multiple of 4 in [4, %lld]", (long long)D,
+                 (long long)molclr::kBandMaxDim);
   MOLCLR_REQUIRE(impl >= -1 && impl <= 1, "gine_aggregate_bwd: impl %d (-1, 0 or 1)", impl);
   hipStream_t s = molclr::as_stream(stream);
   int d4 = (int)(D / 4);
@@ -1472,7 +1475,9 @@ MOLCLR_API int molclr_gine_aggregate_bwd_bf16(const uint16_t* g, const int32_t* 
                                               float* dE2, int64_t N, int64_t D, int accumulate,
                                               void* workspace, size_t workspace_bytes,
                                               molclr_stream_t stream) {
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gine_aggregate_bwd_bf16: dim must be a multiple of 4");
+  MOLCLR_REQUIRE(molclr::band_dim_ok(D),
+                 "gine_aggregate_bwd_bf16: dim %lld must be a multiple of 4 in [4, %lld]",
+                 (long long)D, (long long)molclr::kBandMaxDim);
   hipStream_t s = molclr::as_stream(stream);
   const int d4 = (int)(D / 4);
   if (dx && N > 0) {

@@ -74,8 +74,17 @@ struct Band {
   int band;     // rows per block iteration
   int threads;  // band * d4, rounded up to a multiple of 64
 };
+// The widths a band kernel takes: whole float4 columns, and at most 1024 of
+// them (a block of band * d4 <= 1024 threads holds at least one whole row).
+// Every entry point that plans a band refuses any other width first.
+constexpr int64_t kBandMaxDim = 4096;
+inline bool band_dim_ok(int64_t dim) { return dim >= 4 && dim % 4 == 0 && dim <= kBandMaxDim; }
 inline Band make_band(int64_t dim) {
   Band b;
+  // clamped, so that a width nobody checked still plans a block (d4 >= 1,
+  // band >= 1) and cannot divide by zero on the host
+  if (dim < 4) dim = 4;
+  if (dim > kBandMaxDim) dim = kBandMaxDim;
   b.d4 = (int)(dim / 4);
   int band = 256 / b.d4;
   if (band < 1) band = 1;

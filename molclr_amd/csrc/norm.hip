@@ -807,13 +807,17 @@ __global__ __launch_bounds__(1024) void k_sum(const float* __restrict__ x, float
 // shared with aggregate.hip
 // ---------------------------------------------------------------------------
 size_t molclr_colsum_ws(int64_t rows, int64_t cols) {
+  if (!molclr::band_dim_ok(cols)) return 0;  // no column sum of this width: nothing to reserve
   molclr::Band b = molclr::make_band(cols);
   return (size_t)band_parts(rows, b.band) * cols * sizeof(float) + 256;
 }
 
 int molclr_colsum_impl(const float* X, float* out, int64_t rows, int64_t cols, int64_t ld,
                        int accumulate, molclr::Workspace& w, hipStream_t s) {
-  MOLCLR_REQUIRE(cols > 0 && cols % 4 == 0 && ld % 4 == 0, "colsum: cols/ld must be multiples of 4");
+  MOLCLR_REQUIRE(molclr::band_dim_ok(cols),
+                 "colsum: cols %lld must be a multiple of 4 in [4, %lld]", (long long)cols,
+                 (long long)molclr::kBandMaxDim);
+  MOLCLR_REQUIRE(ld % 4 == 0, "colsum: ld %lld must be a multiple of 4", (long long)ld);
   molclr::Band b = molclr::make_band(cols);
   int64_t P = band_parts(rows, b.band);
   float* partial = w.take<float>(P * cols);
@@ -838,6 +842,9 @@ MOLCLR_API size_t molclr_colsum_f32_workspace_bytes(int64_t rows, int64_t cols) 
 MOLCLR_API int molclr_colsum_f32(const float* X, float* out, int64_t rows, int64_t cols,
                                  int64_t ld, int accumulate, void* workspace,
                                  size_t workspace_bytes, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(molclr::band_dim_ok(cols),
+                 "colsum: cols %lld must be a multiple of 4 in [4, %lld]", (long long)cols,
+                 (long long)molclr::kBandMaxDim);
   MOLCLR_REQUIRE_WS(workspace_bytes, molclr_colsum_ws(rows, cols));
   molclr::Workspace w(workspace, workspace_bytes);
   return molclr_colsum_impl(X, out, rows, cols, ld, accumulate, w, molclr::as_stream(stream));
@@ -853,6 +860,8 @@ int make_segs(int nseg, const int64_t* seg_rows, const int64_t* drows, int64_t c
               Segs& sg, int64_t& P, int64_t& rows) {
   MOLCLR_REQUIRE(nseg >= 1 && nseg <= MOLCLR_MAX_SEGMENTS && (seg_rows || drows),
                  "batchnorm: %d segments (1..%d)", nseg, MOLCLR_MAX_SEGMENTS);
+  MOLCLR_REQUIRE(molclr::band_dim_ok(D), "batchnorm: dim %lld must be a multiple of 4 in [4, %lld]",
+                 (long long)D, (long long)molclr::kBandMaxDim);
   const molclr::Band b = molclr::make_band(D);
   sg.n = nseg;
   sg.band = b.band;
@@ -906,7 +915,6 @@ int bn_fwd_coeffs(const void* zv, const float* gamma, const float* beta, float* 
   Segs& sg = plan.sg;
   int64_t P = 0, rows = 0;
   if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "batchnorm_fwd: dim must be a multiple of 4");
   for (int q = 0; q < nseg && !drows; ++q)  // device-sized: the caller's contract
     MOLCLR_REQUIRE(!training || seg_rows[q] > 1,
                    "batchnorm_fwd: need more than 1 row per segment when training");
@@ -993,7 +1001,6 @@ int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* bet
   Segs sg;
   int64_t P = 0, rows = 0;
   if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "batchnorm_bwd: dim must be a multiple of 4");
   MOLCLR_REQUIRE(rows > 0 && dyv && zv && save_mean && save_invstd && dzv, "batchnorm_bwd: bad args");
   for (int q = 0; q < nseg && !drows; ++q)
     MOLCLR_REQUIRE(seg_rows[q] > 0, "batchnorm_bwd: empty segment");
@@ -1045,7 +1052,8 @@ int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* bet
 // Workspace that covers any split of `rows` rows into <= MOLCLR_MAX_SEGMENTS
 // segments (the encoder executors size their scratch before knowing it).
 size_t molclr_batchnorm_ws_bound(int64_t rows, int64_t D) {
-  const molclr::Band b = molclr::make_band(D > 0 ? D : 4);
+  if (!molclr::band_dim_ok(D)) return 0;
+  const molclr::Band b = molclr::make_band(D);
   return bn_ws_bytes(band_parts_bound(rows, b.band, MOLCLR_MAX_SEGMENTS), D, MOLCLR_MAX_SEGMENTS);
 }
 
@@ -1053,7 +1061,7 @@ MOLCLR_API size_t molclr_batchnorm_seg_workspace_bytes(int nseg, const int64_t* 
                                                        int64_t D) {
   Segs sg;
   int64_t P = 0, rows = 0;
-  if (make_segs(nseg, seg_rows, nullptr, 0, D > 0 ? D : 4, sg, P, rows)) return 0;
+  if (!seg_rows || make_segs(nseg, seg_rows, nullptr, 0, D, sg, P, rows)) return 0;
   return bn_ws_bytes(P, D, nseg);
 }
 
@@ -1115,8 +1123,8 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_max(const float* dy, const float* z, con
 // per segment as the host-sized calls, so the results are bit-identical to
 // them on the real rows.  Workspace: molclr_batchnorm_seg_dev_workspace_bytes.
 MOLCLR_API size_t molclr_batchnorm_seg_dev_workspace_bytes(int nseg, int64_t rows_cap, int64_t D) {
-  if (nseg < 1 || nseg > MOLCLR_MAX_SEGMENTS) return 0;
-  const molclr::Band b = molclr::make_band(D > 0 ? D : 4);
+  if (nseg < 1 || nseg > MOLCLR_MAX_SEGMENTS || !molclr::band_dim_ok(D)) return 0;
+  const molclr::Band b = molclr::make_band(D);
   return bn_ws_bytes(band_parts_bound(rows_cap, b.band, nseg), D, nseg);
 }
 

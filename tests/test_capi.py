@@ -80,3 +80,59 @@ def test_torch_ops_registered():
         assert hasattr(torch.ops.molclr, name), name
     schema = str(torch.ops.molclr.gine_aggregate.default._schema)
     assert schema.startswith("molclr::gine_aggregate(Tensor h, Tensor E1, Tensor E2")
+
+
+_BAND_CHILD = r"""
+import json
+from molclr_amd import _lib
+lib = _lib.load()
+out = {}
+def err():
+    return lib.molclr_last_error().decode()
+for w in (0, 2, 4100):
+    out["colsum_ws_%d" % w] = int(lib.molclr_colsum_f32_workspace_bytes(100, w))
+    rc = lib.molclr_colsum_f32(None, None, 100, w, w, 0, None, 0, None)
+    out["colsum_%d" % w] = [rc, err()]
+for w in (2, 4100):
+    out["bn_ws_%d" % w] = int(lib.molclr_batchnorm_workspace_bytes(100, w))
+    rc = lib.molclr_batchnorm_fwd(None, None, None, None, None, None, None, None, None, 100, w,
+                                  0.1, 1e-5, 1, 0, None, 0, None)
+    out["bn_%d" % w] = [rc, err()]
+    out["agg_ws_%d" % w] = int(lib.molclr_gine_aggregate_bwd_workspace_bytes(100, w))
+    rc = lib.molclr_gine_aggregate_bwd(None, None, None, None, None, None, None, None, 100, w, 0,
+                                       None, 0, None)
+    out["agg_%d" % w] = [rc, err()]
+# the supported range is unchanged at its ends
+out["colsum_ws_4"] = int(lib.molclr_colsum_f32_workspace_bytes(100, 4))
+out["colsum_ws_4096"] = int(lib.molclr_colsum_f32_workspace_bytes(100, 4096))
+print("BAND " + json.dumps(out))
+"""
+
+
+def test_band_width_is_refused_not_divided_by(lib):
+    """A width make_band() cannot plan (dim < 4: d4 == 0; dim > 4096: band == 0)
+    divided by zero on the host.  Every entry point that plans a band now
+    refuses it with MOLCLR_ERR_ARG and its workspace query returns 0.  Run in a
+    child process: a SIGFPE must not take the test process with it."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _BAND_CHILD], cwd=str(ROOT), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("BAND ")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0][5:])
+    for w in (0, 2, 4100):
+        assert out["colsum_ws_%d" % w] == 0
+        rc, msg = out["colsum_%d" % w]
+        assert rc == -1 and "cols %d " % w in msg, (w, rc, msg)
+    for w in (2, 4100):
+        assert out["bn_ws_%d" % w] == 0 and out["agg_ws_%d" % w] == 0
+        for key in ("bn_%d", "agg_%d"):
+            rc, msg = out[key % w]
+            assert rc == -1 and "dim %d " % w in msg, (key, w, rc, msg)
+    # P * cols floats + 256: 100 rows are one partition at band 256 (cols 4)
+    # and ceil(100 / 16) = 7 at band 1 (cols 4096)
+    assert out["colsum_ws_4"] == 1 * 4 * 4 + 256
+    assert out["colsum_ws_4096"] == 7 * 4096 * 4 + 256
