@@ -1233,6 +1233,33 @@ int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
                           float* dh, float* dE, float* dweight, float* dbias, int acc_dE,
                           int acc_dweight, int acc_dbias, void* workspace, size_t workspace_bytes,
                           molclr_stream_t stream);
+/* Device-sized form, for a captured step whose item count changes from replay
+ * to replay: the same kernels over an item CAPACITY T_cap in place of T.
+ * T_cap sizes every buffer, grid and the workspace
+ * (molclr_motif_pool_cap_workspace_bytes); alpha is [T_cap + B] with the h
+ * rows' weights at T_cap + b; clique_idx, sorted_idx and order hold T_cap
+ * entries.  The item count is read on the device as mol_ptr[B]: the rule is
+ * 0 = p_0 <= ... <= p_B <= T_cap, and a mol_ptr that breaks it sets
+ * MOLCLR_STATUS_MOTIF_RANGE and gives NaN rows as above.  Items [p_B, T_cap)
+ * are padding of any value: never an index, no contribution to a, dh, dE,
+ * dweight or dbias wherever the stable sort of all T_cap ids put them; a table
+ * row that only padding names is 0 without acc_dE and untouched with it.
+ * Arithmetic and summation orders are the host-sized form's: on the same items
+ * both give bit-identical results.  molclr_stage_motif fills the buffers. */
+size_t molclr_motif_pool_cap_workspace_bytes(int64_t B, int64_t T_cap, int64_t F);
+int molclr_motif_pool_fwd_cap(const float* h, const float* E, const int64_t* clique_idx,
+                              const int32_t* mol_ptr, const float* gate_weight,
+                              const float* gate_bias, int64_t B, int64_t T_cap, int64_t F,
+                              int64_t num_motifs, float* a, float* alpha, int32_t* status,
+                              molclr_stream_t stream);
+int molclr_motif_pool_bwd_cap(const float* da, const float* h, const float* E,
+                              const int64_t* clique_idx, const int32_t* mol_ptr,
+                              const int64_t* sorted_idx, const int64_t* order,
+                              const float* gate_weight, const float* a, const float* alpha,
+                              int64_t B, int64_t T_cap, int64_t F, int64_t num_motifs, float* dh,
+                              float* dE, float* dweight, float* dbias, int acc_dE, int acc_dweight,
+                              int acc_dbias, void* workspace, size_t workspace_bytes,
+                              molclr_stream_t stream);
 
 /* ---- Captured fine-tuning step (molclr_amd/finetune_step.py) -----------------
  * The fine-tuning loops (finetune.py:89-102 a training batch, finetune.py:259-317
@@ -1254,8 +1281,27 @@ int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
  *     (double)*loss * B to *loss_acc, ORs *status_src (nullable) into
  *     *status_acc and sets *cursor = n + B.  If n + B > capacity (rows of
  *     pred_all / target_all) nothing is stored, the cursor and the sum stay,
- *     and MOLCLR_STATUS_EVAL_OVERFLOW is set in *status_acc. */
+ *     and MOLCLR_STATUS_EVAL_OVERFLOW is set in *status_acc.
+ *   molclr_stage_motif (outside the captured region; one launch): the motif
+ *     model's items -- mol_idx int64 [T + B] (the molecule of every item,
+ *     ascending, then 0 .. B - 1) and clique_idx int64 [T] -- into the buffers
+ *     molclr_motif_pool_*_cap read: clique [T_cap] (the ids, then
+ *     MOLCLR_MOTIF_PAD, which no table holds), mol_ptr int32 [B + 1] (the
+ *     first item of every molecule, by binary search), sorted_idx / order
+ *     [T_cap] (the stable sort of clique by id, padding last; a rank sort, no
+ *     scratch memory).  T > T_cap, a mol_idx[:T] that does not ascend and a
+ *     mol_idx value outside [0, B) set MOLCLR_STATUS_ITEM_OVERFLOW, _ORDER and
+ *     _MOL in *status (nullable; ORed) and make every mol_ptr entry -1, which
+ *     the pool answers with MOLCLR_STATUS_MOTIF_RANGE and NaN rows; nothing is
+ *     stored outside the buffers. */
 #define MOLCLR_STATUS_EVAL_OVERFLOW 64 /* status bit: evaluation rows past the capacity */
+#define MOLCLR_STATUS_ITEM_OVERFLOW 128 /* status bit: more motif items than the capacity */
+#define MOLCLR_STATUS_ITEM_ORDER 256    /* status bit: mol_idx[:T] not ascending */
+#define MOLCLR_STATUS_ITEM_MOL 512      /* status bit: mol_idx outside [0, B) */
+#define MOLCLR_MOTIF_PAD INT64_MAX      /* a padding item's id */
+int molclr_stage_motif(const int64_t* mol_idx, const int64_t* clique_idx, int64_t T, int64_t B,
+                       int64_t T_cap, int64_t* clique, int32_t* mol_ptr, int64_t* sorted_idx,
+                       int64_t* order, int32_t* status, molclr_stream_t stream);
 int molclr_stage_task(const molclr_stage_source* src, const molclr_graph_staged_segment* dst,
                       int64_t* x_all, int64_t num_nodes_cap, int64_t num_edges_cap,
                       int64_t* counts, const void* target_src, void* target_dst,

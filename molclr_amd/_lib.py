@@ -198,6 +198,13 @@ SIGNATURES = {
                                       _P]),
     "molclr_motif_pool_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64,
                                       _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "molclr_motif_pool_cap_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
+    "molclr_motif_pool_fwd_cap": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P,
+                                          _P, _P]),
+    "molclr_motif_pool_bwd_cap": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64,
+                                          _I64, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t,
+                                          _P]),
+    "molclr_stage_motif": (c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "molclr_stage_task": (c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, c_int, _P]),
     "molclr_task_step_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "molclr_eval_tail": (c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
@@ -216,6 +223,10 @@ STATUS_ATOM_RANGE = 8  # MOLCLR_STATUS_ATOM_RANGE
 STATUS_LABEL_RANGE = 16  # MOLCLR_STATUS_LABEL_RANGE
 STATUS_MOTIF_RANGE = 32  # MOLCLR_STATUS_MOTIF_RANGE
 STATUS_EVAL_OVERFLOW = 64  # MOLCLR_STATUS_EVAL_OVERFLOW
+STATUS_ITEM_OVERFLOW = 128  # MOLCLR_STATUS_ITEM_OVERFLOW
+STATUS_ITEM_ORDER = 256  # MOLCLR_STATUS_ITEM_ORDER
+STATUS_ITEM_MOL = 512  # MOLCLR_STATUS_ITEM_MOL
+MOTIF_PAD = 2 ** 63 - 1  # MOLCLR_MOTIF_PAD
 TASK_HEAD_MAX_LAYERS = 10
 TASK_HEAD_MAX_CLASSES = 16
 TASK_HEAD_MAX_DIM = 2044

@@ -3,6 +3,10 @@
 // finetune.py:259-317 for an evaluation pass):
 //   molclr_stage_task       outside the graph: the batch and its targets into
 //                           the fixed buffers a replay reads (one launch)
+//   molclr_stage_motif      outside the graph: the motif model's items into
+//                           fixed buffers of an item capacity, with mol_ptr and
+//                           the stable sort by motif id the pool's backward
+//                           reads (one launch)
 //   molclr_task_step_tail   the training graph's closing launch
 //   molclr_eval_tail        the evaluation graph's closing launch: gathers
 //                           the batch's predictions, targets and loss behind a
@@ -46,7 +50,89 @@ __global__ __launch_bounds__(256) void k_eval_tail(
   }
 }
 
+constexpr int kItemThreads = 256;
+
+// A batch's motif items into buffers of capacity T_cap.  Thread i owns staged
+// position i: its id v_i is clique_idx[i] or, from T on, the padding value, and
+// its place in the stable sort is its rank -- the number of positions j with
+// (v_j, j) < (v_i, i) -- counted over LDS tiles of the ids, which every block
+// reads from the source itself (no block waits for another).  Block 0 also
+// checks mol_idx and writes mol_ptr; T is 0 here when the items were refused.
+__global__ __launch_bounds__(kItemThreads) void k_stage_motif(
+    const int64_t* __restrict__ mol_idx, const int64_t* __restrict__ clique_idx, int64_t T,
+    int64_t rows, int64_t B, int64_t T_cap, int64_t* __restrict__ clique,
+    int32_t* __restrict__ mol_ptr, int64_t* __restrict__ sorted_idx, int64_t* __restrict__ order,
+    int32_t* status, int32_t refused) {
+  __shared__ int64_t s_v[kItemThreads];
+  const int64_t i = (int64_t)blockIdx.x * kItemThreads + threadIdx.x;
+  const int64_t v = i < T ? clique_idx[i] : MOLCLR_MOTIF_PAD;
+  int64_t rank = 0;
+  for (int64_t j0 = 0; j0 < T_cap; j0 += kItemThreads) {
+    const int64_t j = j0 + threadIdx.x;
+    s_v[threadIdx.x] = j < T ? clique_idx[j] : MOLCLR_MOTIF_PAD;
+    __syncthreads();
+    const int n = (int)(T_cap - j0 < kItemThreads ? T_cap - j0 : kItemThreads);
+    for (int q = 0; q < n; ++q) {
+      const int64_t u = s_v[q];
+      rank += (u < v || (u == v && j0 + q < i)) ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  if (i < T_cap) {  // rank is a permutation of [0, T_cap)
+    clique[i] = v;
+    sorted_idx[rank] = v;
+    order[rank] = i;
+  }
+  if (blockIdx.x != 0) return;
+  // mol_idx: [rows] values in [0, B), the first T of them ascending
+  __shared__ int32_t s_bits;
+  if (threadIdx.x == 0) s_bits = refused;
+  __syncthreads();
+  int32_t mine = 0;
+  for (int64_t k = threadIdx.x; k < rows; k += kItemThreads) {
+    const int64_t m = mol_idx[k];
+    if (m < 0 || m >= B) mine |= MOLCLR_STATUS_ITEM_MOL;
+    if (k > 0 && k < T && mol_idx[k - 1] > m) mine |= MOLCLR_STATUS_ITEM_ORDER;
+  }
+  if (mine) atomicOr(&s_bits, mine);
+  __syncthreads();
+  const int32_t bits = s_bits;
+  if (bits && threadIdx.x == 0 && status) atomicOr(status, bits);
+  for (int64_t b = threadIdx.x; b <= B; b += kItemThreads) {
+    int64_t lo = 0, hi = T;  // first item of a molecule >= b
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (mol_idx[mid] < b) lo = mid + 1; else hi = mid;
+    }
+    // refused items: a pointer the pool flags, so no molecule's row is trusted
+    mol_ptr[b] = bits ? -1 : (int32_t)lo;
+  }
+}
+
 }  // namespace
+
+MOLCLR_API int molclr_stage_motif(const int64_t* mol_idx, const int64_t* clique_idx, int64_t T,
+                                  int64_t B, int64_t T_cap, int64_t* clique, int32_t* mol_ptr,
+                                  int64_t* sorted_idx, int64_t* order, int32_t* status,
+                                  molclr_stream_t stream) {
+  MOLCLR_REQUIRE(B >= 1 && B < ((int64_t)1 << 31) && T >= 0 && T_cap >= 0 &&
+                     T_cap < ((int64_t)1 << 31),
+                 "stage_motif: %lld molecules, %lld items, capacity %lld", (long long)B,
+                 (long long)T, (long long)T_cap);
+  MOLCLR_REQUIRE(mol_idx && mol_ptr && (T == 0 || clique_idx) &&
+                     (T_cap == 0 || (clique && sorted_idx && order)),
+                 "stage_motif: null pointer");
+  // more items than the buffers hold: nothing of them is staged
+  const bool over = T > T_cap;
+  int64_t blocks = molclr::ceil_div(T_cap, kItemThreads);
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_stage_motif, dim3((unsigned)blocks), dim3(kItemThreads), 0,
+                     molclr::as_stream(stream), mol_idx, clique_idx, over ? 0 : T,
+                     over ? 0 : T + B, B, T_cap, clique, mol_ptr, sorted_idx, order, status,
+                     over ? MOLCLR_STATUS_ITEM_OVERFLOW : 0);
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
 
 MOLCLR_API int molclr_stage_task(const molclr_stage_source* src,
                                  const molclr_graph_staged_segment* dst, int64_t* x_all,

@@ -50,6 +50,14 @@
 //
 // Plain fp32 fmaf everywhere, no floating-point atomics: results are
 // bit-identical from run to run.
+//
+// Device-sized form (molclr_motif_pool_{fwd,bwd}_cap, for a captured step whose
+// item count changes from replay to replay): the same kernels over an item
+// CAPACITY T_cap.  T_cap sizes alpha ([T_cap + B], the h rows at T_cap + b),
+// the grids and the workspace; the item count is read on the device as
+// mol_ptr[B] (0 = p_0 <= ... <= p_B <= T_cap).  Items [p_B, T_cap) are padding:
+// no segment holds them, and the dE pass skips them wherever the sort put them,
+// so on the same items both forms run the same arithmetic in the same order.
 #include "common.h"
 
 #include <math.h>
@@ -68,9 +76,20 @@ struct PoolArgs {
   const int64_t* idx;
   const int32_t* ptr;
   const float* w;
+  // T: the item capacity -- alpha's h rows start at T, grids and workspace are
+  // sized by it.  The item count is T (dev_count 0) or ptr[B] (dev_count 1).
   int64_t B, T, num_motifs;
   int F;
+  int dev_count;
 };
+
+// the item count; -1 for a device count outside [0, capacity]
+__device__ __forceinline__ int64_t item_count(const int32_t* ptr, int64_t B, int64_t cap,
+                                              int dev_count) {
+  if (!dev_count) return cap;
+  const int64_t t = ptr[B];
+  return t >= 0 && t <= cap ? t : -1;
+}
 
 __device__ __forceinline__ float group_sum16(float v) {
   v += __shfl_xor(v, 8, kGroup);
@@ -87,11 +106,13 @@ __device__ __forceinline__ float wave_sum64(float v) {
 }
 
 // number of motif items of molecule b, first item in p0; -1 for a mol_ptr
-// that does not describe consecutive segments of [0, T)
+// that does not describe consecutive segments of [0, item count)
 __device__ __forceinline__ int segment(const PoolArgs& p, int64_t b, int64_t& p0) {
   const int64_t lo = p.ptr[b], hi = p.ptr[b + 1];
+  const int64_t t = item_count(p.ptr, p.B, p.T, p.dev_count);
   p0 = lo;
-  const bool ok = lo >= 0 && hi >= lo && hi <= p.T && (b > 0 || lo == 0) && (b < p.B - 1 || hi == p.T);
+  const bool ok = t >= 0 && lo >= 0 && hi >= lo && hi <= t && (b > 0 || lo == 0) &&
+                  (b < p.B - 1 || hi == t);
   return ok ? (int)(hi - lo) : -1;
 }
 
@@ -318,11 +339,13 @@ struct ParamGrads {
   const int32_t* mol;
   const float* dwp;
   const float* dcp;
+  const int32_t* ptr;  // mol_ptr: the item count with dev_count
   float* dE;
   float* dw;
   float* dc;
   int acc_dE, acc_dw, acc_dc;
-  int64_t B, T, num_motifs;
+  int dev_count;
+  int64_t B, T, num_motifs;  // T: the capacity, as PoolArgs
   int F;
   int64_t run_blocks, zero_blocks;  // then the dw / dc workgroups
 };
@@ -335,13 +358,22 @@ __global__ __launch_bounds__(kThreads) void k_motif_bwd_params(const ParamGrads 
     const int64_t m = g.sorted[blk];
     if (blk > 0 && g.sorted[blk - 1] == m) return;
     if (m < 0 || m >= g.num_motifs) return;  // never an index
+    // items at and past the count are padding: skipped wherever they sorted to
+    int64_t count = item_count(g.ptr, g.B, g.T, g.dev_count);
+    if (count < 0) count = 0;
+    if (g.dev_count && g.acc_dE) {  // a row only padding names stays as it is
+      bool real = false;
+      for (int64_t q = blk; q < g.T && g.sorted[q] == m && !real; ++q)
+        real = g.order[q] >= 0 && g.order[q] < count;
+      if (!real) return;
+    }
     float* out = g.dE + (size_t)m * F;
     for (int k = threadIdx.x; k < F; k += kThreads) {
       float acc = 0.f;
       const float wk = g.w[k];
       for (int64_t q = blk; q < g.T && g.sorted[q] == m; ++q) {
         const int64_t i = g.order[q];
-        if (i < 0 || i >= g.T) continue;
+        if (i < 0 || i >= count) continue;
         const int64_t mb = g.mol[i];
         if (mb < 0 || mb >= g.B) continue;  // an item no valid segment holds
         acc += fmaf(g.alpha[i], g.da[(size_t)mb * F + k], g.dgate[i] * wk);
@@ -392,7 +424,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 int fill_args(PoolArgs& p, const float* h, const float* E, const int64_t* clique_idx,
               const int32_t* mol_ptr, const float* w, int64_t B, int64_t T, int64_t F,
-              int64_t num_motifs, const char* who) {
+              int64_t num_motifs, bool dev_count, const char* who) {
   MOLCLR_REQUIRE(B >= 1 && B < ((int64_t)1 << 31), "%s: %lld molecules (1 .. 2^31 - 1)", who,
                  (long long)B);
   MOLCLR_REQUIRE(T >= 0 && T < ((int64_t)1 << 31), "%s: %lld items (0 .. 2^31 - 1)", who,
@@ -412,6 +444,7 @@ int fill_args(PoolArgs& p, const float* h, const float* E, const int64_t* clique
   p.T = T;
   p.num_motifs = num_motifs;
   p.F = (int)F;
+  p.dev_count = dev_count ? 1 : 0;
   return MOLCLR_OK;
 }
 
@@ -430,15 +463,17 @@ MOLCLR_API size_t molclr_motif_pool_workspace_bytes(int64_t B, int64_t T, int64_
   return bwd_bytes(B, T, F);
 }
 
-MOLCLR_API int molclr_motif_pool_fwd(const float* h, const float* E, const int64_t* clique_idx,
-                                     const int32_t* mol_ptr, const float* gate_weight,
-                                     const float* gate_bias, int64_t B, int64_t T, int64_t F,
-                                     int64_t num_motifs, float* a, float* alpha, int32_t* status,
-                                     molclr_stream_t stream) {
+namespace {
+
+// both forms: T is the item count (dev_count false) or the capacity
+int pool_fwd(const float* h, const float* E, const int64_t* clique_idx, const int32_t* mol_ptr,
+             const float* gate_weight, const float* gate_bias, int64_t B, int64_t T, int64_t F,
+             int64_t num_motifs, float* a, float* alpha, int32_t* status, bool dev_count,
+             molclr_stream_t stream, const char* who) {
   PoolArgs p;
   MOLCLR_TRY_RC(fill_args(p, h, E, clique_idx, mol_ptr, gate_weight, B, T, F, num_motifs,
-                          "motif_pool_fwd"));
-  MOLCLR_REQUIRE(gate_bias && a && alpha, "motif_pool_fwd: null gate bias / a / alpha");
+                          dev_count, who));
+  MOLCLR_REQUIRE(gate_bias && a && alpha, "%s: null gate bias / a / alpha", who);
   const bool vec = F % 4 == 0 && aligned16(h) && aligned16(E) && aligned16(gate_weight) && aligned16(a);
   hipStream_t s = molclr::as_stream(stream);
   if (vec)
@@ -451,23 +486,20 @@ MOLCLR_API int molclr_motif_pool_fwd(const float* h, const float* E, const int64
   return MOLCLR_OK;
 }
 
-MOLCLR_API int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
-                                     const int64_t* clique_idx, const int32_t* mol_ptr,
-                                     const int64_t* sorted_idx, const int64_t* order,
-                                     const float* gate_weight, const float* a,
-                                     const float* alpha, int64_t B, int64_t T, int64_t F,
-                                     int64_t num_motifs, float* dh, float* dE,
-                                     float* dweight, float* dbias, int acc_dE, int acc_dweight,
-                                     int acc_dbias, void* workspace, size_t workspace_bytes,
-                                     molclr_stream_t stream) {
+int pool_bwd(const float* da, const float* h, const float* E, const int64_t* clique_idx,
+             const int32_t* mol_ptr, const int64_t* sorted_idx, const int64_t* order,
+             const float* gate_weight, const float* a, const float* alpha, int64_t B, int64_t T,
+             int64_t F, int64_t num_motifs, float* dh, float* dE, float* dweight, float* dbias,
+             int acc_dE, int acc_dweight, int acc_dbias, void* workspace, size_t workspace_bytes,
+             bool dev_count, molclr_stream_t stream, const char* who) {
   PoolArgs p;
   MOLCLR_TRY_RC(fill_args(p, h, E, clique_idx, mol_ptr, gate_weight, B, T, F, num_motifs,
-                          "motif_pool_bwd"));
-  MOLCLR_REQUIRE(da && a && alpha, "motif_pool_bwd: null da / a / alpha");
+                          dev_count, who));
+  MOLCLR_REQUIRE(da && a && alpha, "%s: null da / a / alpha", who);
   MOLCLR_REQUIRE(!dE || T == 0 || (sorted_idx && order),
-                 "motif_pool_bwd: dE needs the items sorted by motif id");
+                 "%s: dE needs the items sorted by motif id", who);
   MOLCLR_REQUIRE_WS(workspace_bytes, bwd_bytes(B, T, F));
-  MOLCLR_REQUIRE(workspace, "motif_pool_bwd: null workspace");
+  MOLCLR_REQUIRE(workspace, "%s: null workspace", who);
   molclr::Workspace ws(workspace, workspace_bytes);
   SegGrads g;
   g.da = da;
@@ -480,7 +512,7 @@ MOLCLR_API int molclr_motif_pool_bwd(const float* da, const float* h, const floa
   g.dwp = dweight ? dwp : nullptr;
   g.dcp = ws.take<float>((size_t)B);
   if (!ws.ok()) {
-    molclr::set_error("motif_pool_bwd: workspace too small");
+    molclr::set_error("%s: workspace too small", who);
     return MOLCLR_ERR_WORKSPACE;
   }
   const bool vec = F % 4 == 0 && aligned16(h) && aligned16(E) && aligned16(da) && aligned16(a);
@@ -501,6 +533,8 @@ MOLCLR_API int molclr_motif_pool_bwd(const float* da, const float* h, const floa
   q.mol = g.mol;
   q.dwp = dwp;
   q.dcp = g.dcp;
+  q.ptr = mol_ptr;
+  q.dev_count = p.dev_count;
   q.dE = dE;
   q.dw = dweight;
   q.dc = dbias;
@@ -515,10 +549,62 @@ MOLCLR_API int molclr_motif_pool_bwd(const float* da, const float* h, const floa
   q.zero_blocks = dE && !acc_dE ? molclr::ceil_div(num_motifs, kZeroRows) : 0;
   const int64_t blocks = q.run_blocks + q.zero_blocks +
                          (dweight || dbias ? molclr::ceil_div(F, kThreads) : 0);
-  MOLCLR_REQUIRE(blocks < ((int64_t)1 << 31), "motif_pool_bwd: grid too large");
+  MOLCLR_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large", who);
   if (blocks > 0) {
     hipLaunchKernelGGL(k_motif_bwd_params, dim3((unsigned)blocks), dim3(kThreads), 0, s, q);
     MOLCLR_LAUNCHED();
   }
   return MOLCLR_OK;
+}
+
+}  // namespace
+
+MOLCLR_API int molclr_motif_pool_fwd(const float* h, const float* E, const int64_t* clique_idx,
+                                     const int32_t* mol_ptr, const float* gate_weight,
+                                     const float* gate_bias, int64_t B, int64_t T, int64_t F,
+                                     int64_t num_motifs, float* a, float* alpha, int32_t* status,
+                                     molclr_stream_t stream) {
+  return pool_fwd(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, B, T, F, num_motifs, a, alpha,
+                  status, false, stream, "motif_pool_fwd");
+}
+
+MOLCLR_API int molclr_motif_pool_bwd(const float* da, const float* h, const float* E,
+                                     const int64_t* clique_idx, const int32_t* mol_ptr,
+                                     const int64_t* sorted_idx, const int64_t* order,
+                                     const float* gate_weight, const float* a,
+                                     const float* alpha, int64_t B, int64_t T, int64_t F,
+                                     int64_t num_motifs, float* dh, float* dE,
+                                     float* dweight, float* dbias, int acc_dE, int acc_dweight,
+                                     int acc_dbias, void* workspace, size_t workspace_bytes,
+                                     molclr_stream_t stream) {
+  return pool_bwd(da, h, E, clique_idx, mol_ptr, sorted_idx, order, gate_weight, a, alpha, B, T, F,
+                  num_motifs, dh, dE, dweight, dbias, acc_dE, acc_dweight, acc_dbias, workspace,
+                  workspace_bytes, false, stream, "motif_pool_bwd");
+}
+
+MOLCLR_API size_t molclr_motif_pool_cap_workspace_bytes(int64_t B, int64_t T_cap, int64_t F) {
+  return molclr_motif_pool_workspace_bytes(B, T_cap, F);
+}
+
+MOLCLR_API int molclr_motif_pool_fwd_cap(const float* h, const float* E, const int64_t* clique_idx,
+                                         const int32_t* mol_ptr, const float* gate_weight,
+                                         const float* gate_bias, int64_t B, int64_t T_cap,
+                                         int64_t F, int64_t num_motifs, float* a, float* alpha,
+                                         int32_t* status, molclr_stream_t stream) {
+  return pool_fwd(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, B, T_cap, F, num_motifs, a,
+                  alpha, status, true, stream, "motif_pool_fwd_cap");
+}
+
+MOLCLR_API int molclr_motif_pool_bwd_cap(const float* da, const float* h, const float* E,
+                                         const int64_t* clique_idx, const int32_t* mol_ptr,
+                                         const int64_t* sorted_idx, const int64_t* order,
+                                         const float* gate_weight, const float* a,
+                                         const float* alpha, int64_t B, int64_t T_cap, int64_t F,
+                                         int64_t num_motifs, float* dh, float* dE, float* dweight,
+                                         float* dbias, int acc_dE, int acc_dweight, int acc_dbias,
+                                         void* workspace, size_t workspace_bytes,
+                                         molclr_stream_t stream) {
+  return pool_bwd(da, h, E, clique_idx, mol_ptr, sorted_idx, order, gate_weight, a, alpha, B, T_cap,
+                  F, num_motifs, dh, dE, dweight, dbias, acc_dE, acc_dweight, acc_dbias, workspace,
+                  workspace_bytes, true, stream, "motif_pool_bwd_cap");
 }

@@ -215,6 +215,12 @@ def raise_for_status(st: int) -> None:
                         "(the reference's nn.Embedding raises IndexError)")
         if st & _lib.STATUS_EVAL_OVERFLOW:
             what.append("more evaluation rows than the gather buffers' capacity")
+        if st & _lib.STATUS_ITEM_OVERFLOW:
+            what.append("more motif items than the staged buffers' capacity")
+        if st & _lib.STATUS_ITEM_ORDER:
+            what.append("mol_idx of the motif items not ascending")
+        if st & _lib.STATUS_ITEM_MOL:
+            what.append("mol_idx outside [0, number of molecules)")
         raise ValueError("invalid graph batch: " + ", ".join(what))
 
 

@@ -23,7 +23,10 @@ reference's BRICS cliques.  Optional keys ``log_root``, ``ckpt_root``,
 ``seed`` and ``hip_graph`` (default False): with ``hip_graph: True`` the
 training step and the evaluation passes are replayed from HIP graphs
 (molclr_amd.finetune_step); a model those cannot take trains eagerly after
-one RuntimeWarning.  Invalid inputs (graph indices, atom features, class
+one RuntimeWarning.  The motif model is taken with ``hip_graph_motif: True``
+(default False) next to ``hip_graph: True``: the batch's items from
+molclr_amd.motifs.motif_batch are then staged next to the batch; without that
+key it warns and trains eagerly.  Invalid inputs (graph indices, atom features, class
 labels, motif indices) raise at the next log step (``check_inputs``), as in
 molclr_amd.molclr.
 """
@@ -146,6 +149,7 @@ class FineTune(object):
         # hip_graph: the captured step objects of the model being trained
         # (_captured_for); None while the loop runs eagerly
         self.hip_graph = bool(config.get('hip_graph', False))
+        self.hip_graph_motif = bool(config.get('hip_graph_motif', False))
         self._captured = None
 
     def _get_device(self):
@@ -249,13 +253,18 @@ class FineTune(object):
         return model
 
     # -- one batch ----------------------------------------------------------------
+    def _motif_of(self, data):
+        """The motif model's (mol_idx, clique_idx) of a host batch, on the
+        device; the index tensors are built from the host copy of mol_index."""
+        from .motifs import motif_batch
+        return motif_batch(data.mol_index, self.assignments, self.device)
+
     def _to_device(self, data):
         """(data on the device, the motif model's (mol_idx, clique_idx) or
-        None); the index tensors are built from the host copy of mol_index."""
+        None)."""
         motif = None
         if self.config['model_type'] == 'gin_motif':
-            from .motifs import motif_batch
-            motif = motif_batch(data.mol_index, self.assignments, self.device)
+            motif = self._motif_of(data)
         return data.to(self.device), motif
 
     def _step(self, model, data, motif=None):
@@ -296,7 +305,7 @@ class FineTune(object):
         c = self._captured
         if c is None or c[0] is not model:
             from .finetune_step import CapturedEval, unsupported_reason
-            reason = unsupported_reason(model)
+            reason = unsupported_reason(model, motif_items=self.hip_graph_motif)
             if reason is not None:
                 warnings.warn(f"hip_graph: True -- {reason}; fine-tuning runs eagerly",
                               RuntimeWarning, stacklevel=3)
@@ -314,7 +323,8 @@ class FineTune(object):
         captured = self._captured_for(model, optimizers)
         if captured is not None:
             # the step's loss is its own buffer, overwritten by the next replay
-            return captured[0].step(data.to(self.device)).clone()
+            data, motif = self._to_device(data)
+            return captured[0].step(data, *(motif or ())).clone()
         data, motif = self._to_device(data)
         for opt in optimizers:
             opt.zero_grad()
@@ -384,7 +394,8 @@ class FineTune(object):
         the de-normalised prediction."""
         captured = self._captured_for(model)
         if captured is not None:
-            total, predictions, labels = captured[1].run(loader)
+            motif = self._motif_of if self.config['model_type'] == 'gin_motif' else None
+            total, predictions, labels = captured[1].run(loader, motif)
             model.train()
             self.check_inputs()
         else:

@@ -27,9 +27,17 @@ gather buffers, the staged targets and the task head's ticket word
 (ops.CAPTURE_HEAD_SYNC: one per step object, made before the capture -- the
 capture stream is not the stream the dry run ran on).
 
-Single process only: fine-tuning has no data-parallel path.  The motif model
-(ginet_finetune_mp) is not taken: its item count varies per batch and
-ops.motif_pool has no device-sized form.
+The motif model (ginet_finetune_mp) is taken too.  Its item count varies per
+batch, so its graphs run the device-sized pool (ops.motif_pool_staged) over an
+item capacity: a second staging launch (``molclr_stage_motif``) puts the
+batch's ``(mol_idx, clique_idx)`` into fixed buffers with ``mol_ptr`` and the
+stable sort by motif id the pool's backward reads, and the bucket key gets a
+fourth term, the item capacity (``item_quantum``).  ``step`` and ``run`` take
+the items next to the batch.  The trainer opts in with ``hip_graph_motif:
+True`` next to ``hip_graph: True``; ``hip_graph: True`` alone keeps warning
+and training the motif model eagerly, as before.
+
+Single process only: fine-tuning has no data-parallel path.
 """
 from __future__ import annotations
 
@@ -44,24 +52,43 @@ from .data import _num_graphs_of, raise_for_status
 from .graph_step import StagedPairGraph, _Captured, _round_up
 
 
-def unsupported_reason(model) -> str | None:
-    """Why the captured steps cannot take ``model`` (None: they can)."""
+def unsupported_reason(model, motif_items: bool = False) -> str | None:
+    """Why the captured steps cannot take ``model`` (None: they can).  The
+    motif model is taken only by a caller that hands over every batch's items
+    (``motif_items=True``: ``step(data, mol_idx, clique_idx)``, ``run(loader,
+    motif=...)``); asked without, the answer names the items, as it did before
+    the pool had a device-sized form."""
     from .ginet_finetune import FinetuneReadout
     from .ginet_finetune_mp import GINet as MotifGINet
-    if isinstance(model, MotifGINet):
-        return "the motif model's item count varies per batch (no device-sized motif_pool)"
     if not isinstance(model, FinetuneReadout):
         return "the model has no loss_staged"
     if not model.use_executor or model.num_layer > 16:
         return "the encoder executor is off"
     if model._dim_pad():
         return f"emb_dim {model.emb_dim} needs padding to the kernels' width"
+    if isinstance(model, MotifGINet) and not motif_items:
+        return ("the motif model's item count varies per batch: its captured steps take the "
+                "batch's items (motif_items)")
     lins, _ = model._head_layers()
-    dims = [model.emb_dim, model.feat_dim] + [m.out_features for m in lins]
-    if not ops.task_head_fused(dims):
-        return (f"a task head of widths {dims} is composed from separate launches "
-                f"(fused up to {_lib.TASK_HEAD_MAX_DIM})")
+    if isinstance(model, MotifGINet):
+        # three chains: feat_lin, motif_lin, and pred_head over cat(h, hp)
+        if not ops.MOTIF_POOL:
+            return ("MOLCLR_MOTIF_POOL=0 composes the motif pool from torch ops, which has no "
+                    "device-sized form")
+        chains = [[model.emb_dim, model.feat_dim], [model.feat_dim, model.feat_dim],
+                  [2 * model.feat_dim] + [m.out_features for m in lins]]
+    else:
+        chains = [[model.emb_dim, model.feat_dim] + [m.out_features for m in lins]]
+    for dims in chains:
+        if not ops.task_head_fused(dims):
+            return (f"a task head of widths {dims} is composed from separate launches "
+                    f"(fused up to {_lib.TASK_HEAD_MAX_DIM})")
     return None
+
+
+def _is_motif(model) -> bool:
+    from .ginet_finetune_mp import GINet as MotifGINet
+    return isinstance(model, MotifGINet)
 
 
 class StagedTaskGraph(StagedPairGraph):
@@ -104,6 +131,45 @@ class StagedTaskGraph(StagedPairGraph):
         self._keep = [x, ei, ea, b, y]
 
 
+class StagedMotifGraph(StagedTaskGraph):
+    """A StagedTaskGraph that also holds the motif model's items in buffers of
+    ``item_cap`` entries, written by ``stage_items``: ``clique`` (the ids,
+    then _lib.MOTIF_PAD), ``mol_ptr`` int32 [B + 1] (the item count on the
+    device: ``mol_ptr[B]``), ``sorted_idx`` / ``order`` (the stable sort by
+    id, padding last).  ``item_status`` ORs the staging's refusal bits."""
+
+    def __init__(self, device, node_cap: int, edge_cap: int, graphs: int, labels: bool, cols: int,
+                 item_cap: int):
+        super().__init__(device, node_cap, edge_cap, graphs, labels, cols)
+        self.item_cap = int(item_cap)
+        i64 = dict(dtype=torch.long, device=device)
+        self.clique = torch.full((self.item_cap,), _lib.MOTIF_PAD, **i64)
+        self.sorted_idx = torch.full((self.item_cap,), _lib.MOTIF_PAD, **i64)
+        self.order = torch.arange(self.item_cap, **i64)
+        self.mol_ptr = torch.zeros(graphs + 1, dtype=torch.int32, device=device)
+        self.item_status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep_items = []
+
+    def stage_items(self, mol_idx, clique_idx) -> None:
+        """The batch's ``mol_idx`` [T + B] and ``clique_idx`` [T] in, one launch
+        on the current stream; the inputs stay alive until the next."""
+        B = self.graphs_per_segment[0]
+        if mol_idx.dim() != 1 or clique_idx.dim() != 1 or \
+                mol_idx.shape[0] != clique_idx.shape[0] + B:
+            raise ValueError(f"mol_idx must be [T + B] and clique_idx [T] with B = {B}; got "
+                             f"{tuple(mol_idx.shape)} and {tuple(clique_idx.shape)}")
+        T = int(clique_idx.shape[0])
+        if T > self.item_cap:
+            raise ValueError(f"StagedMotifGraph: {T} items, built for {self.item_cap}")
+        mol_idx = mol_idx.to(self.device, torch.long).contiguous()
+        clique_idx = clique_idx.to(self.device, torch.long).contiguous()
+        _lib.call("molclr_stage_motif", mol_idx.data_ptr(), clique_idx.data_ptr(), T, B,
+                  self.item_cap, self.clique.data_ptr(), self.mol_ptr.data_ptr(),
+                  self.sorted_idx.data_ptr(), self.order.data_ptr(), self.item_status.data_ptr(),
+                  _lib.stream_of(self.device))
+        self._keep_items = [mol_idx, clique_idx]
+
+
 class _CapturedTask:
     """What the two step objects share: the buckets, their lookup and the
     capture discipline of graph_step.CapturedTrainStep (dry run first, a
@@ -111,7 +177,7 @@ class _CapturedTask:
     generation bumped before and after)."""
 
     def __init__(self, model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
-                 node_slack, edge_headroom, device=None):
+                 node_slack, edge_headroom, device=None, item_quantum: int = 256):
         from .ginet_finetune import TASK_LOSS
         if not hasattr(model, "loss_staged"):
             raise TypeError(f"{type(self).__name__}: the model has no loss_staged")
@@ -124,6 +190,9 @@ class _CapturedTask:
         self.node_quantum, self.edge_quantum = int(node_quantum), int(edge_quantum)
         self.node_slack = 2 * self.node_quantum if node_slack is None else int(node_slack)
         self.edge_headroom = float(edge_headroom)
+        # the motif model: keys carry a fourth term, the item capacity
+        self.motif = _is_motif(model)
+        self.item_quantum = int(item_quantum)
         self.max_graphs = int(max_graphs)
         self._graphs: OrderedDict = OrderedDict()
         self.captures = 0
@@ -147,38 +216,54 @@ class _CapturedTask:
         raise NotImplementedError
 
     # -- buckets ---------------------------------------------------------------
-    @staticmethod
-    def _need(data) -> tuple:
-        """(nodes, edges, molecules) of a batch, or of a size tuple."""
+    def _need(self, data, items=None) -> tuple:
+        """(nodes, edges, molecules) of a batch, or of a size tuple; for the
+        motif model a fourth term, the number of motif items (``items``: the
+        count, ``(mol_idx, clique_idx)``, or the size tuple's fourth term)."""
         if isinstance(data, tuple):
-            n, e, g = data
-            return int(n), int(e), int(g)
-        return int(data.x.shape[0]), int(data.edge_index.shape[1]), _num_graphs_of(data)
+            need = tuple(int(v) for v in data)
+        else:
+            need = (int(data.x.shape[0]), int(data.edge_index.shape[1]), _num_graphs_of(data))
+        if not self.motif:
+            return need[:3]
+        if len(need) == 4:
+            return need
+        if items is None:
+            raise TypeError("the motif model's step needs the batch's items "
+                            "(mol_idx, clique_idx)")
+        t = items if isinstance(items, int) else int(items[1].shape[0])
+        return need + (int(t),)
 
-    def bucket(self, data) -> tuple:
-        """(node_cap, edge_cap, molecules) a new capture for this batch gets."""
-        n, e, g = self._need(data)
+    def bucket(self, data, items=None) -> tuple:
+        """(node_cap, edge_cap, molecules) a new capture for this batch gets;
+        (node_cap, edge_cap, molecules, item_cap) for the motif model."""
+        n, e, g, *t = self._need(data, items)
         e_cap = _round_up(int(e * (1.0 + self.edge_headroom)) + 1, self.edge_quantum)
-        return (_round_up(n, self.node_quantum), e_cap, g)
+        key = (_round_up(n, self.node_quantum), e_cap, g)
+        return key + (_round_up(t[0], self.item_quantum),) if t else key
 
-    def pick(self, keys, data):
-        """Of the captured ``keys`` (node_cap, edge_cap, molecules), the one
-        this batch replays on: the smallest that holds it with the same
+    def pick(self, keys, data, items=None):
+        """Of the captured ``keys`` (node_cap, edge_cap, molecules[, item_cap]),
+        the one this batch replays on: the smallest that holds it with the same
         molecule count (a partial last batch is a bucket of its own) and a
         node capacity within ``node_slack`` rows of the batch's own rounded
-        size; None when none does."""
-        n, e, g = self._need(data)
+        size; None when none does.  The motif model's item capacity must hold
+        the batch's items; among keys equal in nodes and edges the smallest
+        does."""
+        n, e, g, *t = self._need(data, items)
         limit = _round_up(n, self.node_quantum) + self.node_slack
         best = None
         for k in keys:
             if k[0] >= n and k[1] >= e and k[0] <= limit and k[2] == g:
-                if best is None or k[:2] < best[:2]:
+                if t and k[3] < t[0]:
+                    continue
+                if best is None or k[:2] + k[3:] < best[:2] + best[3:]:
                     best = k
         return best
 
-    def lookup(self, data):
+    def lookup(self, data, items=None):
         """The captured entry this batch would replay on, or None."""
-        k = self.pick(list(self._graphs), data)
+        k = self.pick(list(self._graphs), data, items)
         return None if k is None else self._graphs[k]
 
     def _insert(self, key, ent) -> None:
@@ -186,23 +271,25 @@ class _CapturedTask:
         if len(self._graphs) > self.max_graphs:
             self._graphs.popitem(last=False)
 
-    def _entry(self, data):
+    def _entry(self, data, items=None):
         self._make_state()
-        k = self.pick(list(self._graphs), data)
+        k = self.pick(list(self._graphs), data, items)
         if k is None:
-            k = self.bucket(data)
-            self._insert(k, self._capture(k, data))  # stages this batch too
+            k = self.bucket(data, items)
+            self._insert(k, self._capture(k, data, items))  # stages this batch too
             return self._graphs[k], True
         self._graphs.move_to_end(k)  # least-recently-replayed eviction
         return self._graphs[k], False
 
-    def prepare(self, batches) -> int:
+    def prepare(self, batches, motif=None) -> int:
         """Capture (without running) every graph the given batches need;
-        returns the number of new captures."""
+        returns the number of new captures.  ``motif`` (the motif model): a
+        callable from a host batch to its ``(mol_idx, clique_idx)``."""
         before = self.captures
         with self._mode():
             for data in batches:
-                self._entry(data.to(self.device) if self.device is not None else data)
+                items = motif(data) if self.motif else None
+                self._entry(data.to(self.device) if self.device is not None else data, items)
         return self.captures - before
 
     def _mode(self):
@@ -211,7 +298,7 @@ class _CapturedTask:
 
     @property
     def buckets(self) -> list:
-        """(node_cap, edge_cap, molecules) of every live capture."""
+        """(node_cap, edge_cap, molecules[, item_cap]) of every live capture."""
         return list(self._graphs)
 
     # -- capture ---------------------------------------------------------------
@@ -228,16 +315,25 @@ class _CapturedTask:
         eager loop uses (FineTune._step) -- the same arithmetic by construction."""
         return self.normalizer.norm(graph.target) if self.normalizer else graph.target
 
-    def _capture(self, key, data=None) -> _Captured:
-        reason = unsupported_reason(self.model)
+    def _stage(self, graph, data, items) -> None:
+        graph.stage_task(data)
+        if self.motif:
+            graph.stage_items(*items)
+
+    def _capture(self, key, data=None, items=None) -> _Captured:
+        reason = unsupported_reason(self.model, motif_items=self.motif)
         if reason is None and not self.model._executor_ok():
             reason = "the encoder executor does not take the model's BatchNorm / dropout settings"
         if reason:
             raise NotImplementedError(f"{type(self).__name__}: {reason}")
         ops._check_no_timer()
-        graph = StagedTaskGraph(self.device, key[0], key[1], key[2], self.labels, self.out_dim)
+        if self.motif:
+            graph = StagedMotifGraph(self.device, key[0], key[1], key[2], self.labels,
+                                     self.out_dim, key[3])
+        else:
+            graph = StagedTaskGraph(self.device, key[0], key[1], key[2], self.labels, self.out_dim)
         if data is not None:
-            graph.stage_task(data)
+            self._stage(graph, data, items)
         for opt in self._optimizers():
             opt.sync_lr()
         # the capture must record the weight-plane regeneration: make every
@@ -272,10 +368,10 @@ class _CapturedTask:
         ops.bump_param_generation()
         return _Captured(graph, g, keep)
 
-    def _replay(self, data):
-        ent, fresh = self._entry(data)
+    def _replay(self, data, items=None):
+        ent, fresh = self._entry(data, items)
         if not fresh:
-            ent.graph.stage_task(data)
+            self._stage(ent.graph, data, items)
             for opt in self._optimizers():
                 opt.sync_lr()
         ent.cuda_graph.replay()
@@ -286,7 +382,11 @@ class _CapturedTask:
     def check(self) -> None:
         """Raise ValueError if any replayed batch so far had invalid inputs."""
         self._make_state()
-        raise_for_status(int(self.status.item()))
+        st = int(self.status.item())
+        if self.motif:  # the item staging's own refusals
+            for ent in self._graphs.values():
+                st |= int(ent.graph.item_status.item())
+        raise_for_status(st)
 
     def close(self) -> None:
         """Release every captured graph (and its pool's memory) now."""
@@ -312,7 +412,10 @@ class CapturedFinetuneStep(_CapturedTask):
     model's task); ``normalizer`` (finetune.Normalizer) is applied to float
     targets inside the graph.  Buckets are keyed (node capacity, edge
     capacity, molecules): lookup as graph_step.CapturedTrainStep's, and a
-    partial last batch gets a bucket of its own.
+    partial last batch gets a bucket of its own.  The motif model's step is
+    ``step(data, mol_idx, clique_idx)`` and its keys carry a fourth term, the
+    item capacity (``item_quantum``): a batch with more items than a bucket
+    holds replays on a larger one or captures it.
 
     The returned loss is this object's own buffer, overwritten by the next
     step.  ``status`` ORs every replayed batch's validity word -- graph
@@ -321,7 +424,7 @@ class CapturedFinetuneStep(_CapturedTask):
 
     def __init__(self, model, optimizers, criterion=None, normalizer=None, node_quantum: int = 256,
                  edge_quantum: int = 2048, max_graphs: int = 16, node_slack: int | None = None,
-                 edge_headroom: float = 0.04):
+                 edge_headroom: float = 0.04, item_quantum: int = 256):
         from .optim import FusedAdam
         if isinstance(optimizers, FusedAdam):
             optimizers = [optimizers]
@@ -330,7 +433,7 @@ class CapturedFinetuneStep(_CapturedTask):
             raise TypeError("CapturedFinetuneStep needs one or two molclr_amd.optim.FusedAdam "
                             "(learning rate and step counter on the device)")
         super().__init__(model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
-                         node_slack, edge_headroom, optimizers[0].flat.device)
+                         node_slack, edge_headroom, optimizers[0].flat.device, item_quantum)
         self.optimizers = optimizers
 
     def _optimizers(self):
@@ -359,10 +462,13 @@ class CapturedFinetuneStep(_CapturedTask):
                   _lib.stream_of(self.device))
         return pred, loss
 
-    def step(self, data) -> torch.Tensor:
+    def step(self, data, mol_idx=None, clique_idx=None) -> torch.Tensor:
         if not self.model.training:
             raise RuntimeError("CapturedFinetuneStep: the model must be in training mode")
-        self._replay(data)
+        if self.motif and (mol_idx is None or clique_idx is None):
+            raise TypeError("CapturedFinetuneStep: the motif model's step takes "
+                            "(data, mol_idx, clique_idx)")
+        self._replay(data, (mol_idx, clique_idx) if self.motif else None)
         # the replay's Adam steps changed the weights behind Python's back
         ops.bump_param_generation()
         return self.loss
@@ -380,7 +486,9 @@ class CapturedEval(_CapturedTask):
     and adds ``loss * B`` to an fp64 sum in the loop's order; the pass ends
     with one synchronisation and one device-to-host copy.  Predictions are
     de-normalised after the copy.  ``predictions`` is float32 [n, C],
-    ``labels`` the flattened targets (int64 or float32), both numpy.
+    ``labels`` the flattened targets (int64 or float32), both numpy.  For the
+    motif model ``run(loader, motif=fn)`` takes a callable from a host batch to
+    its ``(mol_idx, clique_idx)``.
 
     ``capacity``: rows the gather buffers hold.  None (the default) sizes them
     by the loader and grows them when a larger one comes (the graphs are
@@ -392,9 +500,10 @@ class CapturedEval(_CapturedTask):
 
     def __init__(self, model, criterion=None, normalizer=None, capacity: int | None = None,
                  node_quantum: int = 256, edge_quantum: int = 2048, max_graphs: int = 16,
-                 node_slack: int | None = None, edge_headroom: float = 0.04):
+                 node_slack: int | None = None, edge_headroom: float = 0.04,
+                 item_quantum: int = 256):
         super().__init__(model, criterion, normalizer, node_quantum, edge_quantum, max_graphs,
-                         node_slack, edge_headroom)
+                         node_slack, edge_headroom, None, item_quantum)
         self.fixed = capacity is not None
         self.capacity = int(capacity) if self.fixed else 0
         self._sticky = 0  # status bits of earlier passes (check())
@@ -461,7 +570,10 @@ class CapturedEval(_CapturedTask):
         s = getattr(loader, "sampler", None)
         return len(s) if s is not None and hasattr(s, "__len__") else None
 
-    def run(self, loader):
+    def run(self, loader, motif=None):
+        if self.motif and motif is None:
+            raise TypeError("CapturedEval: the motif model's pass takes motif=callable, from a "
+                            "host batch to its (mol_idx, clique_idx)")
         self._make_state()
         if not self.fixed:
             rows = self._rows_of(loader)
@@ -473,7 +585,8 @@ class CapturedEval(_CapturedTask):
         self._buf[:self._HEADER].zero_()
         with self._mode():
             for data in loader:
-                self._replay(data.to(self.device))
+                items = motif(data) if self.motif else None
+                self._replay(data.to(self.device), items)
         host = self._buf.cpu()  # the pass's one synchronisation and one copy
         cursor, loss_acc, status, pred, tgt = self._views(host)
         self._sticky |= int(status.item())
@@ -489,4 +602,5 @@ class CapturedEval(_CapturedTask):
         raise_for_status(self._sticky)
 
 
-__all__ = ["CapturedEval", "CapturedFinetuneStep", "StagedTaskGraph", "unsupported_reason"]
+__all__ = ["CapturedEval", "CapturedFinetuneStep", "StagedMotifGraph", "StagedTaskGraph",
+           "unsupported_reason"]

@@ -105,25 +105,34 @@ class GINet(FinetuneReadout, ginet_molclr.GINet):
             values = self._segment_values[key] = torch.arange(B + 1, device=mol_idx.device)
         return torch.searchsorted(mol_idx[:T].contiguous(), values).to(torch.int32)
 
-    def _task(self, data, mol_idx, clique_idx, loss=None, target=None):
-        h, graph = self._embed(data)
+    def _motif_readout(self, h, graph, pool, loss=None, target=None):
+        """Everything after the encoder: pooling + feat_lin, the attention pool
+        ``pool(h)``, motif_lin and ``cat(h, hp)`` through the pred_head chain."""
         pooled, W = self._pool(h, graph)
         h = ops.task_head(pooled, [W], [self.feat_lin.bias], [None])[0]
-        B, T = h.shape[0], clique_idx.shape[0]
-        if mol_idx.dim() != 1 or clique_idx.dim() != 1 or mol_idx.shape[0] != T + B:
-            raise ValueError(f"mol_idx must be [T + B] = [{T} + {B}] and clique_idx [T]; got "
-                             f"{tuple(mol_idx.shape)} and {tuple(clique_idx.shape)}")
-        mol_idx = mol_idx.to(h.device, torch.long)
-        clique_idx = clique_idx.to(h.device, torch.long)
-        gate = self.motif_pool.gate_nn[0]
-        a = ops.motif_pool(h, self.motif_embedding.weight, clique_idx,
-                           self._mol_ptr(mol_idx, T, B), gate.weight, gate.bias, graph.status)
+        a = pool(h)
         hp = ops.task_head(a, [self.motif_lin.weight], [self.motif_lin.bias], [None])[0]
         x = torch.cat((h, hp), dim=1)
         lins, acts = self._head_layers()
         _, pred, loss = ops.task_head(x, [m.weight for m in lins], [m.bias for m in lins], acts,
                                       loss, target, graph.status)
         return x, pred, loss
+
+    def _task(self, data, mol_idx, clique_idx, loss=None, target=None):
+        h, graph = self._embed(data)
+        B, T = graph.num_graphs, clique_idx.shape[0]
+        if mol_idx.dim() != 1 or clique_idx.dim() != 1 or mol_idx.shape[0] != T + B:
+            raise ValueError(f"mol_idx must be [T + B] = [{T} + {B}] and clique_idx [T]; got "
+                             f"{tuple(mol_idx.shape)} and {tuple(clique_idx.shape)}")
+        mol_idx = mol_idx.to(h.device, torch.long)
+        clique_idx = clique_idx.to(h.device, torch.long)
+        gate = self.motif_pool.gate_nn[0]
+
+        def pool(hm):
+            return ops.motif_pool(hm, self.motif_embedding.weight, clique_idx,
+                                  self._mol_ptr(mol_idx, T, B), gate.weight, gate.bias,
+                                  graph.status)
+        return self._motif_readout(h, graph, pool, loss, target)
 
     def forward(self, data, mol_idx, clique_idx):
         """``(cat(h, hp) [B, 2 * feat_dim], pred [B, 2 | 1])``; pred stays
@@ -138,5 +147,23 @@ class GINet(FinetuneReadout, ginet_molclr.GINet):
         return self._task(data, mol_idx, clique_idx, criterion or TASK_LOSS[self.task], target)
 
     def loss_staged(self, graph, target, criterion=None):
-        raise NotImplementedError("the motif model has no staged form: its item count varies "
-                                  "per batch and ops.motif_pool has no device-sized form")
+        """:meth:`loss` over a staged graph that also carries the batch's items
+        (molclr_amd.finetune_step.StagedMotifGraph): ``graph.clique`` /
+        ``mol_ptr`` / ``sorted_idx`` / ``order`` are buffers of a fixed item
+        capacity, the item count stays on the device, and the pool is
+        ops.motif_pool_staged -- no sort, no searchsorted and no shape that
+        follows the batch, so the step can be captured."""
+        if not self._executor_ok() or self._dim_pad():
+            raise NotImplementedError("loss_staged needs the encoder executor at a width "
+                                      "the kernels take unpadded")
+        if getattr(graph, "clique", None) is None:
+            raise NotImplementedError("the motif model has no staged form without the batch's "
+                                      "items in the graph (finetune_step.StagedMotifGraph)")
+        gate = self.motif_pool.gate_nn[0]
+
+        def pool(hm):
+            return ops.motif_pool_staged(hm, self.motif_embedding.weight, graph.clique,
+                                         graph.mol_ptr, graph.sorted_idx, graph.order,
+                                         gate.weight, gate.bias, graph.status)
+        return self._motif_readout(self._run_encoder(graph.x, graph), graph, pool,
+                                   criterion or TASK_LOSS[self.task], target)

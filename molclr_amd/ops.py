@@ -1699,3 +1699,86 @@ def motif_pool(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status=None):
     if not MOTIF_POOL:
         return _motif_pool_composed(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status)
     return _MotifPool.apply(h, E, clique_idx, mol_ptr, gate_weight, gate_bias, status)
+
+
+class _MotifPoolCap(torch.autograd.Function):
+    """molclr_motif_pool_fwd_cap / _bwd_cap over staged item buffers: every
+    size is the capacity, the item count stays on the device (mol_ptr[B]) and
+    the sorted items come from the staging -- nothing here follows the batch,
+    so a captured step records it once."""
+
+    @staticmethod
+    def forward(ctx, h, E, clique, mol_ptr, sorted_idx, order, w, c, status):
+        hc, Ec, wc, cc = _c(h), _c(E), _c(w), _c(c)
+        B, F = hc.shape
+        cap = clique.shape[0]
+        dev = hc.device
+        a = torch.empty(B, F, dtype=torch.float32, device=dev)
+        alpha = torch.empty(cap + B, dtype=torch.float32, device=dev)
+        _lib.call("molclr_motif_pool_fwd_cap", hc.data_ptr(), Ec.data_ptr(), clique.data_ptr(),
+                  mol_ptr.data_ptr(), wc.data_ptr(), cc.data_ptr(), B, cap, F, Ec.shape[0],
+                  a.data_ptr(), alpha.data_ptr(), _lib.ptr(status), _stream(hc))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(hc, Ec, clique, mol_ptr, sorted_idx, order, wc, alpha, a)
+        ctx.params = (E, w, c)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        if da is None:
+            return (None,) * 9
+        h, E, clique, mol_ptr, sorted_idx, order, w, alpha, a = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        pE, pw, pc = ctx.params
+        B, F = h.shape
+        cap = clique.shape[0]
+        dev = h.device
+        da = _c(da)
+        dh = torch.empty_like(h) if need[0] else None
+        ebuf = wbuf = cbuf = rE = rw = rc = None
+        eacc = wacc = cacc = 0
+        if need[1]:
+            ebuf, eacc, rE = _grad_sink(pE, E.shape, dev)
+        if need[6]:
+            wbuf, wacc, rw = _grad_sink(pw, pw.shape, dev)
+        if need[7]:
+            cbuf, cacc, rc = _grad_sink(pc, pc.shape, dev)
+        ws_bytes = _wsq("molclr_motif_pool_cap_workspace_bytes", B, cap, F)
+        ws = _ws(ws_bytes, dev)
+        _lib.call("molclr_motif_pool_bwd_cap", da.data_ptr(), h.data_ptr(), E.data_ptr(),
+                  clique.data_ptr(), mol_ptr.data_ptr(), sorted_idx.data_ptr(), order.data_ptr(),
+                  w.data_ptr(), a.data_ptr(), alpha.data_ptr(), B, cap, F, E.shape[0],
+                  _lib.ptr(dh), _lib.ptr(ebuf), _lib.ptr(wbuf), _lib.ptr(cbuf), eacc, wacc, cacc,
+                  ws.data_ptr(), ws_bytes, _stream(h))
+        return dh, rE, None, None, None, None, rw, rc, None
+
+
+def motif_pool_staged(h, E, clique, mol_ptr, sorted_idx, order, gate_weight, gate_bias,
+                      status=None):
+    """:func:`motif_pool` over item buffers of a fixed capacity, as
+    ``molclr_stage_motif`` fills them (finetune_step.StagedMotifGraph):
+    ``clique`` / ``sorted_idx`` / ``order`` int64 [T_cap], ``mol_ptr`` int32
+    [B + 1] with the item count in ``mol_ptr[B]``.  Items from the count on are
+    padding.  On the same items the result and every gradient are bit-identical
+    to :func:`motif_pool`'s.  Fused kernels only: there is no composed form
+    (MOLCLR_MOTIF_POOL=0 is refused)."""
+    _check(h, E, clique, mol_ptr, sorted_idx, order, gate_weight, gate_bias, status)
+    if not MOTIF_POOL:
+        raise NotImplementedError("motif_pool_staged: MOLCLR_MOTIF_POOL=0 composes the pool from "
+                                  "torch ops, which has no device-sized form")
+    if h.dim() != 2 or E.dim() != 2 or E.shape[1] != h.shape[1]:
+        raise ValueError(f"motif_pool_staged: h {tuple(h.shape)} and E {tuple(E.shape)} must be "
+                         "[B, F] and [num_motifs, F]")
+    B, F = h.shape
+    cap = clique.shape[0]
+    for name, t in (("clique", clique), ("sorted_idx", sorted_idx), ("order", order)):
+        if t.dtype != torch.long or t.shape != (cap,) or not t.is_contiguous():
+            raise ValueError(f"motif_pool_staged: {name} must be a contiguous int64 [{cap}]")
+    if mol_ptr.dtype != torch.int32 or mol_ptr.shape != (B + 1,) or not mol_ptr.is_contiguous():
+        raise ValueError(f"motif_pool_staged: mol_ptr must be a contiguous int32 [{B + 1}]")
+    if gate_weight.numel() != F or gate_bias.numel() != 1:
+        raise ValueError("motif_pool_staged: gate_weight must hold F values and gate_bias one")
+    if h.dtype != torch.float32 or E.dtype != torch.float32:
+        raise ValueError("motif_pool_staged: h and E must be float32")
+    return _MotifPoolCap.apply(h, E, clique, mol_ptr, sorted_idx, order, gate_weight, gate_bias,
+                               status)
