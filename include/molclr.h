@@ -22,7 +22,7 @@
  *   - GINEConv edge embedding + message + PyG aggr='add'
  *       models/ginet_molclr.py:39-44        -> molclr_gine_aggregate_fwd / _bwd
  *   - GCNConv message + aggr='add' + bias
- *       models/gcn_molclr.py:72-88          -> molclr_gcn_aggregate_fwd / _bwd
+ *       models/gcn_molclr.py:72-88          -> molclr_gcn_aggregate_fwd / _bwd (and _bf16)
  *   - nn.Linear (GIN MLP ginet_molclr.py:19-23, heads :90-96), GCN `x @ W`
  *       (gcn_molclr.py:76) and their autograd -> molclr_gemm_f32, molclr_colsum_f32
  *   - BatchNorm1d(train/eval) + ReLU + dropout(p=0)
@@ -366,6 +366,24 @@ int molclr_gcn_aggregate_bwd(const float* g, const int32_t* rowptr_t, const int3
                              const uint32_t* nbr_t, const int32_t* ecount, float* dxw, float* dE1, float* dE2,
                              float* dbias, int64_t num_nodes, int64_t dim, int accumulate,
                              void* workspace, size_t workspace_bytes, molclr_stream_t stream);
+/* The same over bf16 storage (see "bf16 storage" below): xw / out and g / dxw
+ * are bf16, the tables, the bias and their gradients fp32.  Per element the
+ * forward does the fp32 kernel's additions in its order and rounds once, to
+ * nearest even, at the store (dim % 8 == 0: 16-byte units; else 8-byte units).
+ * The backward's dxw is molclr_gine_aggregate_bwd_bf16's transposed gather;
+ * dE1 / dE2 / dbias are summed in fp32 / fp64 by the fp32 entry point's kernels
+ * with its partitioning and order, so on the same values they equal its
+ * outputs bit for bit.  workspace: molclr_gcn_aggregate_bwd_workspace_bytes. */
+int molclr_gcn_aggregate_fwd_bf16(const uint16_t* xw, const int32_t* rowptr, const int32_t* col,
+                                  const uint8_t* ecode, const uint32_t* nbr, const float* E1,
+                                  const float* E2, const float* bias, uint16_t* out,
+                                  int64_t num_nodes, int64_t dim, molclr_stream_t stream);
+int molclr_gcn_aggregate_bwd_bf16(const uint16_t* g, const int32_t* rowptr_t,
+                                  const int32_t* col_t, const uint32_t* nbr_t,
+                                  const int32_t* ecount, uint16_t* dxw, float* dE1, float* dE2,
+                                  float* dbias, int64_t num_nodes, int64_t dim, int accumulate,
+                                  void* workspace, size_t workspace_bytes,
+                                  molclr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * FP32 GEMM on the gfx950 f32 MFMA (v_mfma_f32_32x32x2_f32: exact f32 FMA
@@ -972,8 +990,19 @@ typedef struct molclr_gcn_encoder {
   /* 0 = split-bf16 x6 products; 1 = the backward in h3 (as molclr_gin_encoder's
    * bit 0: the weight gradient with per-tensor scales, dx = dxw W^T with
    * row-wise scales; weight_planes_t are then molclr_hplanes_make_batch
-   * images, dim <= 1024). */
+   * images, dim <= 1024).  fp32 storage only. */
   int32_t fp32_gemm;
+  /* MOLCLR_DTYPE_F32 (0, so a zero-initialised struct): fp32 node features.
+   * MOLCLR_DTYPE_BF16 (dim % 8 == 0, fp32_gemm 0): bf16 node features and
+   * activation gradients -- x W and dxw W^T as one bf16 MFMA per product on
+   * plane 0 of weight_planes / weight_planes_t (molclr_gemm_bf16), the bf16
+   * aggregation and BatchNorm, dW through molclr_linear_wgrad_bf16; fp32
+   * statistics, tables, bias and parameter gradients: the reference's
+   * mixed-precision switch for the GCN (molclr.py:16-24,93-96,
+   * finetune.py:180-183).  h_out / dh_out are then bf16.  The field lies in
+   * what was the padding between fp32_gemm and status: the size of the struct
+   * and the offset of every other field are unchanged. */
+  int32_t dtype;
   int32_t* status; /* nullable: MOLCLR_STATUS_ATOM_RANGE, as molclr_gin_encoder */
   double drop_ratio;   /* as molclr_gin_encoder */
   int64_t* drop_state; /* as molclr_gin_encoder */
@@ -992,15 +1021,23 @@ typedef struct molclr_gcn_encoder_grads {
   void* embed_done;
 } molclr_gcn_encoder_grads;
 
+/* Arena (the activations one forward saves for its backward) and workspace
+ * (scratch) of an fp32 encoder (dtype MOLCLR_DTYPE_F32) ... */
 size_t molclr_gcn_encoder_arena_bytes(int num_layer, int64_t num_nodes, int64_t dim);
 size_t molclr_gcn_encoder_workspace_bytes(int num_layer, int64_t num_nodes, int64_t dim);
+/* ... and of an encoder of either storage type (0 for an unknown dtype). */
+size_t molclr_gcn_encoder_arena_bytes_dtype(int num_layer, int64_t num_nodes, int64_t dim,
+                                            int dtype);
+size_t molclr_gcn_encoder_workspace_bytes_dtype(int num_layer, int64_t num_nodes, int64_t dim,
+                                                int dtype);
+/* h_out / dh_out [N,D] in enc->dtype storage, as molclr_gin_encoder_fwd / _bwd. */
 int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* enc, const int64_t* x,
-                           const molclr_device_graph* graph, float* h_out, void* arena,
+                           const molclr_device_graph* graph, void* h_out, void* arena,
                            size_t arena_bytes, void* workspace, size_t workspace_bytes,
                            molclr_stream_t stream);
 int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* enc, const molclr_gcn_encoder_grads* grads,
                            const int64_t* x, const molclr_device_graph* graph,
-                           const float* dh_out, const void* arena, size_t arena_bytes,
+                           const void* dh_out, const void* arena, size_t arena_bytes,
                            void* workspace, size_t workspace_bytes, molclr_stream_t stream);
 
 /* ------------------------------------------------------------------------
@@ -1026,6 +1063,9 @@ int molclr_dropout_mask(const int64_t* key, int layer, double p, uint8_t* keep, 
  * Node features and activation gradients are bf16 ([N,D] of uint16 bit
  * patterns, round-to-nearest-even); all arithmetic, tables, statistics and
  * parameter gradients are fp32.  Same semantics as the fp32 entry points.
+ * The GCN's bf16 entry points (molclr_gcn_aggregate_fwd_bf16 / _bwd_bf16) are
+ * declared next to their fp32 forms; molclr_gcn_encoder.dtype selects the
+ * storage of its executor.
  * ------------------------------------------------------------------------ */
 int molclr_atom_embed_fwd_bf16(const int64_t* x, const float* X1, const float* X2, uint16_t* h,
                                int64_t num_nodes, int64_t dim, int64_t n1, int64_t n2,

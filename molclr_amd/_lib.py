@@ -66,6 +66,9 @@ SIGNATURES = {
     "molclr_gcn_aggregate_bwd_workspace_bytes": (c_size_t, [_I64, _I64]),
     "molclr_gcn_aggregate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int,
                                          _P, c_size_t, _P]),
+    "molclr_gcn_aggregate_fwd_bf16": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
+    "molclr_gcn_aggregate_bwd_bf16": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
+                                              c_int, _P, c_size_t, _P]),
     "molclr_gemm_f32_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
     "molclr_gemm_f32": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, c_int, c_int, c_int,
                                 _P, _P, _I64, _P, c_size_t, _P]),
@@ -156,6 +159,8 @@ SIGNATURES = {
     "molclr_gin_encoder_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "molclr_gcn_encoder_arena_bytes": (c_size_t, [c_int, _I64, _I64]),
     "molclr_gcn_encoder_workspace_bytes": (c_size_t, [c_int, _I64, _I64]),
+    "molclr_gcn_encoder_arena_bytes_dtype": (c_size_t, [c_int, _I64, _I64, c_int]),
+    "molclr_gcn_encoder_workspace_bytes_dtype": (c_size_t, [c_int, _I64, _I64, c_int]),
     "molclr_gcn_encoder_fwd": (c_int, [_P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "molclr_gcn_encoder_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "molclr_dropout_next_key": (c_int, [_P, _P, _P]),
@@ -250,15 +255,16 @@ GIN_LAYER_PARAMS = ("mlp0_weight", "mlp0_bias", "mlp2_weight", "mlp2_bias", "edg
 GCN_LAYER_PARAMS = ("weight", "bias", "edge_embedding1", "edge_embedding2", "bn_weight", "bn_bias")
 
 
-def _encoder_fields(layer_params, planes, tail):
+def _encoder_fields(layer_params, planes, head, tail):
     """struct molclr_{gin,gcn}_encoder: the common head, the per-layer
-    parameter, BatchNorm-buffer and weight-plane pointers, the kind's tail."""
+    parameter, BatchNorm-buffer and weight-plane pointers, the kind's fields
+    before (head) and after (tail) fp32_gemm."""
     return [("num_layer", ctypes.c_int32), ("training", ctypes.c_int32), ("dim", c_int64),
             ("n_atom", c_int64), ("n_chiral", c_int64), ("momentum", c_double),
             ("eps", c_double), ("x_embedding1", c_void_p), ("x_embedding2", c_void_p)] + [
         (f, _L16) for f in layer_params + ("bn_running_mean", "bn_running_var",
-                                           "bn_num_batches_tracked") + planes] + tail + [
-        ("fp32_gemm", ctypes.c_int32), ("status", c_void_p), ("drop_ratio", c_double),
+                                           "bn_num_batches_tracked") + planes] + head + [
+        ("fp32_gemm", ctypes.c_int32)] + tail + [("status", c_void_p), ("drop_ratio", c_double),
         ("drop_state", c_void_p)]
 
 
@@ -272,7 +278,7 @@ class GinEncoder(ctypes.Structure):
     """struct molclr_gin_encoder (include/molclr.h)."""
     _fields_ = _encoder_fields(
         GIN_LAYER_PARAMS, ("mlp0_planes", "mlp0_planes_t", "mlp2_planes", "mlp2_planes_t"),
-        [("dtype", ctypes.c_int32)])
+        [("dtype", ctypes.c_int32)], [])
 
 
 class GinEncoderGrads(ctypes.Structure):
@@ -282,7 +288,10 @@ class GinEncoderGrads(ctypes.Structure):
 
 class GcnEncoder(ctypes.Structure):
     """struct molclr_gcn_encoder (include/molclr.h)."""
-    _fields_ = _encoder_fields(GCN_LAYER_PARAMS, ("weight_planes", "weight_planes_t"), [])
+    # dtype fills the padding between fp32_gemm and status: every other
+    # field's offset, and the struct's size, are those of the struct without it
+    _fields_ = _encoder_fields(GCN_LAYER_PARAMS, ("weight_planes", "weight_planes_t"), [],
+                               [("dtype", ctypes.c_int32)])
 
 
 class GcnEncoderGrads(ctypes.Structure):

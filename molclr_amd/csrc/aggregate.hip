@@ -718,47 +718,54 @@ __global__ __launch_bounds__(1024) void k_gather_ecount(
 // ---------------------------------------------------------------------------
 // GCN aggregation (scalar edge embedding, bias)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float4 gcn_msg(const float4* __restrict__ xw, const float* __restrict__ E1,
-                                          const float* __restrict__ E2, int32_t j, int q, int d4,
-                                          int c) {
-  const float e = E1[q / 3] + E2[q % 3];
-  const float4 v = xw[(int64_t)j * d4 + c];
+// St: the storage of xw / out (StBF16: 8-byte units, the D % 8 != 0 form of
+// molclr_gcn_aggregate_fwd_bf16; D % 8 == 0 takes k_gcn_agg_fwd_b8 below).
+__device__ __forceinline__ float gcn_edge(const float* __restrict__ E1, const float* __restrict__ E2,
+                                          int q) {
+  return E1[q / 3] + E2[q % 3];
+}
+__device__ __forceinline__ float4 f4sadd(float e, float4 v) {
   return make_float4(e + v.x, e + v.y, e + v.z, e + v.w);
 }
 
+template <typename St = StF32>
 __global__ __launch_bounds__(kT) void k_gcn_agg_fwd(
-    const float4* __restrict__ xw, const int32_t* __restrict__ rowptr,
+    const typename St::T* __restrict__ xw, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const uint8_t* __restrict__ ecode,
     const uint4* __restrict__ nbr, const float* __restrict__ E1, const float* __restrict__ E2,
-    const float4* __restrict__ bias, float4* __restrict__ out, int64_t N, int d4) {
+    const float4* __restrict__ bias, typename St::T* __restrict__ out, int64_t N, int d4) {
   int64_t t = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   if (t >= N * d4) return;
   int64_t i = N * d4 < (1ll << 32) ? (int64_t)((uint32_t)t / (uint32_t)d4) : t / d4;
   int c = (int)(t - i * d4);
+  auto msg = [&](int32_t j, int q) {
+    return f4sadd(gcn_edge(E1, E2, q), St::ld(xw, (int64_t)j * d4 + c));
+  };
   const uint4 s = nbr[i];
-  const float4 self = xw[t];
+  const float4 self = St::ld(xw, t);
   const uint32_t deg = nbr_degree(s.x);
   float4 acc = f4zero();
   if (deg <= MOLCLR_NBR_SLOTS) {
-    const float4 m0 = deg > 0 ? gcn_msg(xw, E1, E2, nbr_node(s.x), nbr_ecomb(s.x), d4, c) : acc;
-    const float4 m1 = deg > 1 ? gcn_msg(xw, E1, E2, nbr_node(s.y), nbr_ecomb(s.y), d4, c) : acc;
-    const float4 m2 = deg > 2 ? gcn_msg(xw, E1, E2, nbr_node(s.z), nbr_ecomb(s.z), d4, c) : acc;
-    const float4 m3 = deg > 3 ? gcn_msg(xw, E1, E2, nbr_node(s.w), nbr_ecomb(s.w), d4, c) : acc;
+    const float4 m0 = deg > 0 ? msg(nbr_node(s.x), nbr_ecomb(s.x)) : acc;
+    const float4 m1 = deg > 1 ? msg(nbr_node(s.y), nbr_ecomb(s.y)) : acc;
+    const float4 m2 = deg > 2 ? msg(nbr_node(s.z), nbr_ecomb(s.z)) : acc;
+    const float4 m3 = deg > 3 ? msg(nbr_node(s.w), nbr_ecomb(s.w)) : acc;
     if (deg > 0) acc = f4add(acc, m0);
     if (deg > 1) acc = f4add(acc, m1);
     if (deg > 2) acc = f4add(acc, m2);
     if (deg > 3) acc = f4add(acc, m3);
   } else {
     for (int32_t k = rowptr[i], e = rowptr[i + 1]; k < e; ++k)
-      acc = f4add(acc, gcn_msg(xw, E1, E2, col[k], MOLCLR_ECOMB(ecode[k]), d4, c));
+      acc = f4add(acc, msg(col[k], MOLCLR_ECOMB(ecode[k])));
   }
   const float es = E1[MOLCLR_SELF_LOOP_BOND_TYPE] + E2[0];
-  acc = f4add(acc, make_float4(es + self.x, es + self.y, es + self.z, es + self.w));
-  out[t] = f4add(acc, bias[c]);
+  acc = f4add(acc, f4sadd(es, self));
+  St::st(out, t, f4add(acc, bias[c]));
 }
 
 // One wave per row: rowsum(g_i) weighted by ecount[i][0..8); per-wave fp64 partials.
-__global__ __launch_bounds__(256) void k_rowsum_ecount_partial(const float4* __restrict__ g,
+template <typename St = StF32>
+__global__ __launch_bounds__(256) void k_rowsum_ecount_partial(const typename St::T* __restrict__ g,
                                                                const int32_t* __restrict__ ecount,
                                                                int64_t N, int d4,
                                                                double* __restrict__ partial) {
@@ -771,8 +778,8 @@ __global__ __launch_bounds__(256) void k_rowsum_ecount_partial(const float4* __r
     const int64_t i2 = i + nwaves;
     double s = 0.0, s2 = 0.0;
     for (int c = lane; c < d4; c += 64) {
-      const float4 v = g[i * d4 + c];
-      const float4 v2 = i2 < N ? g[i2 * d4 + c] : f4zero();
+      const float4 v = St::ld(g, i * d4 + c);
+      const float4 v2 = i2 < N ? St::ld(g, i2 * d4 + c) : f4zero();
       s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
       s2 += ((double)v2.x + (double)v2.y) + ((double)v2.z + (double)v2.w);
     }
@@ -948,6 +955,46 @@ __global__ __launch_bounds__(kT) void k_transpose_gather_b8(const uint16_t* __re
   st8(dx, t, f8add(acc, ld8(g, t)));
 }
 
+// k_gcn_agg_fwd over bf16 rows in 16-byte units: the row's slot first, then up
+// to four neighbour units in flight before the ordered adds (the CSR walk past
+// four), the self term last, then the bias; the fp32 kernel's adds in its
+// order, rounded once at the store.
+__global__ __launch_bounds__(kT) void k_gcn_agg_fwd_b8(
+    const uint16_t* __restrict__ xw, const int32_t* __restrict__ rowptr,
+    const int32_t* __restrict__ col, const uint8_t* __restrict__ ecode,
+    const uint4* __restrict__ nbr, const float* __restrict__ E1, const float* __restrict__ E2,
+    const float4* __restrict__ bias, uint16_t* __restrict__ out, int64_t N, int d8) {
+  int64_t t = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
+  if (t >= N * d8) return;
+  const int64_t i = t / d8;
+  const int c = (int)(t - i * d8);
+  auto msg = [&](int32_t j, int q) {
+    const float e = gcn_edge(E1, E2, q);
+    const F8 v = ld8(xw, (int64_t)j * d8 + c);
+    return F8{f4sadd(e, v.a), f4sadd(e, v.b)};
+  };
+  const uint4 s = nbr[i];
+  const F8 self = ld8(xw, t);
+  const uint32_t deg = nbr_degree(s.x);
+  F8 acc = {f4zero(), f4zero()};
+  if (deg <= MOLCLR_NBR_SLOTS) {
+    const F8 m0 = deg > 0 ? msg(nbr_node(s.x), nbr_ecomb(s.x)) : acc;
+    const F8 m1 = deg > 1 ? msg(nbr_node(s.y), nbr_ecomb(s.y)) : acc;
+    const F8 m2 = deg > 2 ? msg(nbr_node(s.z), nbr_ecomb(s.z)) : acc;
+    const F8 m3 = deg > 3 ? msg(nbr_node(s.w), nbr_ecomb(s.w)) : acc;
+    if (deg > 0) acc = f8add(acc, m0);
+    if (deg > 1) acc = f8add(acc, m1);
+    if (deg > 2) acc = f8add(acc, m2);
+    if (deg > 3) acc = f8add(acc, m3);
+  } else {
+    for (int32_t k = rowptr[i], e = rowptr[i + 1]; k < e; ++k)
+      acc = f8add(acc, msg(col[k], MOLCLR_ECOMB(ecode[k])));
+  }
+  const float es = E1[MOLCLR_SELF_LOOP_BOND_TYPE] + E2[0];
+  acc = f8add(acc, F8{f4sadd(es, self.a), f4sadd(es, self.b)});
+  st8(out, t, f8add(acc, F8{bias[2 * c], bias[2 * c + 1]}));
+}
+
 int64_t ecount_parts(int64_t N, int band) {
   int64_t P = molclr::ceil_div(N, (int64_t)band * 8);
   if (P > 1024) P = 1024;
@@ -958,9 +1005,9 @@ constexpr int64_t kRowsumBlocks = 1024;  // 4096 waves, ~2 trips of two rows eac
 
 }  // namespace
 
-// Column sums shared with norm.hip (declared there).
-int molclr_colsum_impl(const float* X, float* out, int64_t rows, int64_t cols, int64_t ld,
-                       int accumulate, molclr::Workspace& w, hipStream_t s);
+// Column sums shared with norm.hip (declared there); X in `dtype` storage.
+int molclr_colsum_impl(const void* X, int dtype, float* out, int64_t rows, int64_t cols,
+                       int64_t ld, int accumulate, molclr::Workspace& w, hipStream_t s);
 size_t molclr_colsum_ws(int64_t rows, int64_t cols);
 
 MOLCLR_API int molclr_atom_embed_fwd(const int64_t* x, const float* X1, const float* X2,
@@ -1233,10 +1280,35 @@ MOLCLR_API int molclr_gcn_aggregate_fwd(const float* xw, const int32_t* rowptr,
   if (N == 0) return MOLCLR_OK;
   MOLCLR_REQUIRE(xw && rowptr && nbr && E1 && E2 && bias && out, "gcn_aggregate_fwd: null pointer");
   int d4 = (int)(D / 4);
-  molclr::launch_timed(molclr::kTimeGcnAgg, k_gcn_agg_fwd,
+  molclr::launch_timed(molclr::kTimeGcnAgg, k_gcn_agg_fwd<StF32>,
                        dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0, molclr::as_stream(stream),
-                       (const float4*)xw, rowptr, col, ecode, (const uint4*)nbr, E1, E2,
-                       (const float4*)bias, (float4*)out, N, d4);
+                       xw, rowptr, col, ecode, (const uint4*)nbr, E1, E2, (const float4*)bias, out,
+                       N, d4);
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+MOLCLR_API int molclr_gcn_aggregate_fwd_bf16(const uint16_t* xw, const int32_t* rowptr,
+                                             const int32_t* col, const uint8_t* ecode,
+                                             const uint32_t* nbr, const float* E1,
+                                             const float* E2, const float* bias, uint16_t* out,
+                                             int64_t N, int64_t D, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gcn_aggregate_fwd_bf16: dim must be a multiple of 4");
+  if (N == 0) return MOLCLR_OK;
+  MOLCLR_REQUIRE(xw && rowptr && nbr && E1 && E2 && bias && out,
+                 "gcn_aggregate_fwd_bf16: null pointer");
+  if (D % 8 == 0) {
+    const int d8 = (int)(D / 8);
+    molclr::launch_timed(molclr::kTimeGcnAgg, k_gcn_agg_fwd_b8, dim3(molclr::ceil_div(N * d8, kT)),
+                         dim3(kT), 0, molclr::as_stream(stream), xw, rowptr, col, ecode,
+                         (const uint4*)nbr, E1, E2, (const float4*)bias, out, N, d8);
+  } else {
+    const int d4 = (int)(D / 4);
+    molclr::launch_timed(molclr::kTimeGcnAgg, k_gcn_agg_fwd<StBF16>,
+                         dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0,
+                         molclr::as_stream(stream), xw, rowptr, col, ecode, (const uint4*)nbr, E1,
+                         E2, (const float4*)bias, out, N, d4);
+  }
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
@@ -1246,35 +1318,71 @@ MOLCLR_API size_t molclr_gcn_aggregate_bwd_workspace_bytes(int64_t N, int64_t D)
   return a + molclr_colsum_ws(N, D);
 }
 
+// molclr_gcn_aggregate_bwd / _bf16: the transposed gather, the ecount-weighted
+// row sums and the bias column sum over g in St's storage (one partitioning
+// and summation order for both, so the fp32 outputs agree bit for bit)
+template <typename St>
+static int gcn_agg_bwd(const char* who, const typename St::T* g, const int32_t* rowptr_t,
+                       const int32_t* col_t, const uint32_t* nbr_t, const int32_t* ecount,
+                       typename St::T* dxw, float* dE1, float* dE2, float* dbias, int64_t N,
+                       int64_t D, int accumulate, void* workspace, size_t workspace_bytes,
+                       hipStream_t s) {
+  constexpr bool bf = St::kBytes == 2;
+  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "%s: dim must be a multiple of 4", who);
+  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_aggregate_bwd_workspace_bytes(N, D));
+  int d4 = (int)(D / 4);
+  if (dxw && N > 0) {
+    MOLCLR_REQUIRE(g && rowptr_t && nbr_t, "%s: null pointer", who);
+    if constexpr (bf) {
+      if (D % 8 == 0)
+        hipLaunchKernelGGL(k_transpose_gather_b8, dim3(molclr::ceil_div(N * (D / 8), kT)), dim3(kT),
+                           0, s, g, rowptr_t, col_t, (const uint4*)nbr_t, dxw, N, (int)(D / 8));
+      else
+        hipLaunchKernelGGL(k_transpose_gather<StBF16>, dim3(molclr::ceil_div(N * d4, kT)),
+                           dim3(kT), 0, s, g, rowptr_t, col_t, (const uint4*)nbr_t, dxw, N, d4);
+    } else {
+      hipLaunchKernelGGL(k_transpose_gather<StF32>, dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0,
+                         s, g, rowptr_t, col_t, (const uint4*)nbr_t, dxw, N, d4);
+    }
+  }
+  molclr::Workspace w(workspace, workspace_bytes);
+  double* partial = w.take<double>(kRowsumBlocks * 4 * 8);
+  if (dE1 || dE2) {
+    MOLCLR_REQUIRE(N == 0 || (g && ecount), "%s: null pointer", who);
+    hipLaunchKernelGGL(k_rowsum_ecount_partial<St>, dim3(kRowsumBlocks), dim3(256), 0, s, g, ecount,
+                       N, d4, partial);
+    hipLaunchKernelGGL(k_reduce_rowsum_partial, dim3(1), dim3(512), 0, s, partial,
+                       kRowsumBlocks * 4, dE1, dE2, accumulate);
+  }
+  MOLCLR_LAUNCHED();
+  if (dbias) {
+    int rc = molclr_colsum_impl(g, bf ? MOLCLR_DTYPE_BF16 : MOLCLR_DTYPE_F32, dbias, N, D, D,
+                                accumulate, w, s);
+    if (rc) return rc;
+  }
+  return MOLCLR_OK;
+}
+
 MOLCLR_API int molclr_gcn_aggregate_bwd(const float* g, const int32_t* rowptr_t,
                                         const int32_t* col_t, const uint32_t* nbr_t,
                                         const int32_t* ecount, float* dxw,
                                         float* dE1, float* dE2, float* dbias, int64_t N,
                                         int64_t D, int accumulate, void* workspace,
                                         size_t workspace_bytes, molclr_stream_t stream) {
-  MOLCLR_REQUIRE(D > 0 && D % 4 == 0, "gcn_aggregate_bwd: dim must be a multiple of 4");
-  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_aggregate_bwd_workspace_bytes(N, D));
-  hipStream_t s = molclr::as_stream(stream);
-  int d4 = (int)(D / 4);
-  if (dxw && N > 0) {
-    MOLCLR_REQUIRE(g && rowptr_t && nbr_t, "gcn_aggregate_bwd: null pointer");
-    hipLaunchKernelGGL(k_transpose_gather<StF32>, dim3(molclr::ceil_div(N * d4, kT)), dim3(kT), 0,
-                       s, g, rowptr_t, col_t, (const uint4*)nbr_t, dxw, N, d4);
-  }
-  molclr::Workspace w(workspace, workspace_bytes);
-  double* partial = w.take<double>(kRowsumBlocks * 4 * 8);
-  if (dE1 || dE2) {
-    hipLaunchKernelGGL(k_rowsum_ecount_partial, dim3(kRowsumBlocks), dim3(256), 0, s,
-                       (const float4*)g, ecount, N, d4, partial);
-    hipLaunchKernelGGL(k_reduce_rowsum_partial, dim3(1), dim3(512), 0, s, partial,
-                       kRowsumBlocks * 4, dE1, dE2, accumulate);
-  }
-  MOLCLR_LAUNCHED();
-  if (dbias) {
-    int rc = molclr_colsum_impl(g, dbias, N, D, D, accumulate, w, s);
-    if (rc) return rc;
-  }
-  return MOLCLR_OK;
+  return gcn_agg_bwd<StF32>("gcn_aggregate_bwd", g, rowptr_t, col_t, nbr_t, ecount, dxw, dE1, dE2,
+                            dbias, N, D, accumulate, workspace, workspace_bytes,
+                            molclr::as_stream(stream));
+}
+
+MOLCLR_API int molclr_gcn_aggregate_bwd_bf16(const uint16_t* g, const int32_t* rowptr_t,
+                                             const int32_t* col_t, const uint32_t* nbr_t,
+                                             const int32_t* ecount, uint16_t* dxw, float* dE1,
+                                             float* dE2, float* dbias, int64_t N, int64_t D,
+                                             int accumulate, void* workspace,
+                                             size_t workspace_bytes, molclr_stream_t stream) {
+  return gcn_agg_bwd<StBF16>("gcn_aggregate_bwd_bf16", g, rowptr_t, col_t, nbr_t, ecount, dxw, dE1,
+                             dE2, dbias, N, D, accumulate, workspace, workspace_bytes,
+                             molclr::as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------

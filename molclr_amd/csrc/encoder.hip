@@ -613,54 +613,62 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
 // GCN encoder executor (models/gcn_molclr.py:140-151), same scheme: per layer
 // xw = x W (scratch), z = gcn_aggregate(xw) + bias (BatchNorm input, saved),
 // h = BatchNorm(z) (+ReLU but the last; the next layer's input, saved).
-// Arena: per layer z_l, h_l [N,D], mean_l / invstd_l [D]; then h0 [N,D] and the
-// dropout key (as the GIN executor's).
-// Workspace: xw / dxw, dz, dh [N,D] x 3, then the entry points' largest.
+// Arena: per layer z_l, h_l [N,D] in the encoder's storage type, mean_l /
+// invstd_l [D] fp32; then h0 [N,D] and the dropout key (as the GIN executor's).
+// Workspace: xw / dxw, dz, dh [N,D] x 3 in the storage type, then the entry
+// points' largest.
+// bf16 storage (dtype MOLCLR_DTYPE_BF16): one bf16 MFMA per product on plane 0
+// of the same weight images, the bf16 aggregation, BatchNorm and weight
+// gradient; no h3 form.
 // ---------------------------------------------------------------------------
 namespace {
 
+// byte offsets, every buffer 256-byte aligned; es: bytes of a node-feature element
 struct GcnArena {
   size_t z[MOLCLR_MAX_LAYERS], h[MOLCLR_MAX_LAYERS], mean[MOLCLR_MAX_LAYERS],
       invstd[MOLCLR_MAX_LAYERS];
-  size_t hmax[MOLCLR_MAX_LAYERS];  // h3: max slot of layer l's input (floats, contiguous)
+  size_t hmax[MOLCLR_MAX_LAYERS];  // h3: max slot of layer l's input (contiguous)
   size_t h0, dropkey, total;  // dropkey: this forward's dropout key (seed, call)
-  GcnArena(int L, int64_t N, int64_t D) {
+  GcnArena(int L, int64_t N, int64_t D, size_t es) {
     size_t used = 0;
-    auto off = [&](size_t count) {
+    auto off = [&](size_t bytes) {
       const size_t o = used;
-      used += (count + 63) / 64 * 64;
+      used += (bytes + 255) / 256 * 256;
       return o;
     };
     for (int l = 0; l < L; ++l) {
-      z[l] = off(N * D);
-      h[l] = off(N * D);
-      mean[l] = off(MOLCLR_MAX_SEGMENTS * D);  // [segment][D]
-      invstd[l] = off(MOLCLR_MAX_SEGMENTS * D);
+      z[l] = off(N * D * es);
+      h[l] = off(N * D * es);
+      mean[l] = off(MOLCLR_MAX_SEGMENTS * D * sizeof(float));  // [segment][D]
+      invstd[l] = off(MOLCLR_MAX_SEGMENTS * D * sizeof(float));
     }
-    const size_t slots = off((size_t)L * kMaxSlotFloats);
-    for (int l = 0; l < L; ++l) hmax[l] = slots + (size_t)l * kMaxSlotFloats;
-    h0 = off(N * D);
-    dropkey = off(2 * sizeof(int64_t) / sizeof(float));
-    total = used * sizeof(float);
+    const size_t slots = off((size_t)L * kMaxSlotFloats * sizeof(float));
+    for (int l = 0; l < L; ++l) hmax[l] = slots + (size_t)l * kMaxSlotFloats * sizeof(float);
+    h0 = off(N * D * es);
+    dropkey = off(2 * sizeof(int64_t));
+    total = used;
   }
 };
 
-size_t gcn_kernels_ws(int64_t N, int64_t D) {
+size_t gcn_kernels_ws(int64_t N, int64_t D, int dtype) {
   size_t m = 0;
   auto mx = [&](size_t v) { m = v > m ? v : m; };
   mx(molclr_gemm_f32_workspace_bytes(N, D, D));  // x W, dxw W^T
   mx(molclr_gemm_f32_workspace_bytes(D, D, N));  // dW = x^T dxw
   mx(molclr_linear_wgrad_workspace_bytes(N, D, D));  // its h3 form
+  if (dtype == MOLCLR_DTYPE_BF16) mx(molclr_linear_wgrad_bf16_workspace_bytes(N, D, D));
   mx(molclr_batchnorm_ws_bound(N, D));
   mx(molclr_gcn_aggregate_bwd_workspace_bytes(N, D));
   mx(molclr_atom_embed_bwd_workspace_bytes(N, D, MOLCLR_NUM_ATOM_TYPE, MOLCLR_NUM_CHIRALITY));
   return m;
 }
-size_t gcn_scratch_floats(int64_t N, int64_t D) { return (size_t)N * D * 3; }
+// xw / dxw, dz, dh [N,D] in the storage type
+size_t gcn_scratch_bytes(int64_t N, int64_t D, size_t es) { return (size_t)N * D * 3 * es; }
 // h3 backward: dxw's row maxima [N] and max slot, after the scratch
 size_t gcn_h3_bytes(int64_t N) {
   return molclr::align_up((size_t)N * sizeof(float), 256) + kMaxSlotFloats * sizeof(float);
 }
+bool gcn_dtype_ok(int dtype) { return dtype == MOLCLR_DTYPE_F32 || dtype == MOLCLR_DTYPE_BF16; }
 
 int check_gcn(const molclr_gcn_encoder* e, const molclr_device_graph* g) {
   MOLCLR_REQUIRE(e && g, "gcn_encoder: null encoder / graph");
@@ -668,6 +676,10 @@ int check_gcn(const molclr_gcn_encoder* e, const molclr_device_graph* g) {
   MOLCLR_REQUIRE(e->num_layer >= 1 && e->num_layer <= MOLCLR_MAX_LAYERS,
                  "gcn_encoder: num_layer %d", e->num_layer);
   MOLCLR_REQUIRE(e->dim > 0 && e->dim % 4 == 0, "gcn_encoder: dim %lld", (long long)e->dim);
+  MOLCLR_REQUIRE(e->dtype == MOLCLR_DTYPE_F32 || (e->dtype == MOLCLR_DTYPE_BF16 && e->dim % 8 == 0),
+                 "gcn_encoder: dtype %d (bf16 needs dim %% 8 == 0)", e->dtype);
+  MOLCLR_REQUIRE(e->dtype == MOLCLR_DTYPE_F32 || e->fp32_gemm == 0,
+                 "gcn_encoder: fp32_gemm %d with bf16 storage", e->fp32_gemm);
   MOLCLR_REQUIRE(e->n_atom == MOLCLR_NUM_ATOM_TYPE && e->n_chiral == MOLCLR_NUM_CHIRALITY,
                  "gcn_encoder: embedding tables must be [%d,D] and [%d,D]",
                  MOLCLR_NUM_ATOM_TYPE, MOLCLR_NUM_CHIRALITY);
@@ -681,19 +693,29 @@ int check_gcn(const molclr_gcn_encoder* e, const molclr_device_graph* g) {
 
 }  // namespace
 
+MOLCLR_API size_t molclr_gcn_encoder_arena_bytes_dtype(int L, int64_t N, int64_t D, int dtype) {
+  if (L < 1 || L > MOLCLR_MAX_LAYERS || !gcn_dtype_ok(dtype)) return 0;
+  return GcnArena(L, N, D, elem_bytes(dtype)).total;
+}
+
+MOLCLR_API size_t molclr_gcn_encoder_workspace_bytes_dtype(int L, int64_t N, int64_t D,
+                                                           int dtype) {
+  (void)L;
+  if (!gcn_dtype_ok(dtype)) return 0;
+  return gcn_scratch_bytes(N, D, elem_bytes(dtype)) + 256 + gcn_h3_bytes(N) +
+         gcn_kernels_ws(N, D, dtype) + 256;
+}
+
 MOLCLR_API size_t molclr_gcn_encoder_arena_bytes(int L, int64_t N, int64_t D) {
-  if (L < 1 || L > MOLCLR_MAX_LAYERS) return 0;
-  return GcnArena(L, N, D).total;
+  return molclr_gcn_encoder_arena_bytes_dtype(L, N, D, MOLCLR_DTYPE_F32);
 }
 
 MOLCLR_API size_t molclr_gcn_encoder_workspace_bytes(int L, int64_t N, int64_t D) {
-  (void)L;
-  return gcn_scratch_floats(N, D) * sizeof(float) + 256 + gcn_h3_bytes(N) + gcn_kernels_ws(N, D) +
-         256;
+  return molclr_gcn_encoder_workspace_bytes_dtype(L, N, D, MOLCLR_DTYPE_F32);
 }
 
 MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t* x,
-                                      const molclr_device_graph* g, float* h_out, void* arena,
+                                      const molclr_device_graph* g, void* h_out, void* arena,
                                       size_t arena_bytes, void* workspace, size_t workspace_bytes,
                                       molclr_stream_t stream) {
   MOLCLR_TRY(check_gcn(e, g));
@@ -703,13 +725,16 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
   SegRows seg;
   MOLCLR_TRY(graph_segments(g, &g->num_nodes, seg));
   MOLCLR_REQUIRE(x && h_out && arena, "gcn_encoder_fwd: null pointer");
-  const GcnArena lay(L, N, D);
+  const bool bf = e->dtype == MOLCLR_DTYPE_BF16;
+  const size_t es = elem_bytes(e->dtype);
+  const GcnArena lay(L, N, D, es);
   MOLCLR_REQUIRE_WS(arena_bytes, lay.total);
-  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_encoder_workspace_bytes(L, N, D));
-  float* A = (float*)arena;
-  float* xw = (float*)workspace;
-  void* kws = (char*)workspace + molclr::align_up(gcn_scratch_floats(N, D) * sizeof(float), 256);
-  const size_t kws_bytes = gcn_kernels_ws(N, D);
+  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_encoder_workspace_bytes_dtype(L, N, D, e->dtype));
+  char* A = (char*)arena;
+  auto F = [&](size_t off) { return (float*)(A + off); };
+  void* xw = workspace;
+  void* kws = (char*)workspace + molclr::align_up(gcn_scratch_bytes(N, D, es), 256);
+  const size_t kws_bytes = gcn_kernels_ws(N, D, e->dtype);
 
   const bool h3 = e->fp32_gemm == 1;
   if (h3 && molclr::zero_async(A + lay.hmax[0], (size_t)L * kMaxSlotFloats * sizeof(float),
@@ -719,30 +744,43 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
   }
   CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);
   MOLCLR_TRY(open_drop(drop, e->drop_state, stream));
-  float* h = A + lay.h0;
-  MOLCLR_TRY(molclr_atom_embed_fwd(x, e->x_embedding1, e->x_embedding2, h, N, D, e->n_atom,
-                                   e->n_chiral, e->status, stream));
+  void* h = A + lay.h0;
+  if (bf)
+    MOLCLR_TRY(molclr_atom_embed_fwd_bf16(x, e->x_embedding1, e->x_embedding2, (uint16_t*)h, N, D,
+                                          e->n_atom, e->n_chiral, e->status, stream));
+  else
+    MOLCLR_TRY(molclr_atom_embed_fwd(x, e->x_embedding1, e->x_embedding2, (float*)h, N, D,
+                                     e->n_atom, e->n_chiral, e->status, stream));
   for (int l = 0; l < L; ++l) {
-    float* z = A + lay.z[l];
+    void* z = A + lay.z[l];
     const bool last = l == L - 1;
-    float* y = last ? h_out : A + lay.h[l];
+    void* y = last ? h_out : A + lay.h[l];
     // x W, W [in, out] as a K-major B (ops.gemm_w(x, W, N, D, D, D, D, False, True))
-    if (h3)  // the same product, also folding max |h| into the layer's slot
-      MOLCLR_TRY(molclr_gemm_f32_bplanes_max(h, e->weight_planes[l], xw, N, D, D, D, D,
-                                             MOLCLR_EPI_NONE, nullptr, nullptr, 0,
-                                             (float*)(A + lay.hmax[l]), nullptr, nullptr, nullptr,
-                                             kws, kws_bytes, stream));
-    else
-      MOLCLR_TRY(molclr_gemm_f32_bplanes(h, e->weight_planes[l], xw, N, D, D, D, D, 0,
-                                       MOLCLR_EPI_NONE, nullptr, nullptr, 0, kws, kws_bytes,
-                                       stream));
-    MOLCLR_TRY(molclr_gcn_aggregate_fwd(xw, g->rowptr, g->col, g->ecode, g->nbr,
-                                        e->edge_embedding1[l], e->edge_embedding2[l], e->bias[l],
-                                        z, N, D, stream));
+    if (bf) {  // plane 0 of the same image: bf16(W), one MFMA per product
+      MOLCLR_TRY(molclr_gemm_bf16((const uint16_t*)h, e->weight_planes[l], (uint16_t*)xw, N, D, D,
+                                  D, D, MOLCLR_EPI_NONE, nullptr, nullptr, 0, stream));
+      MOLCLR_TRY(molclr_gcn_aggregate_fwd_bf16((const uint16_t*)xw, g->rowptr, g->col, g->ecode,
+                                               g->nbr, e->edge_embedding1[l],
+                                               e->edge_embedding2[l], e->bias[l], (uint16_t*)z, N,
+                                               D, stream));
+    } else {
+      if (h3)  // the same product, also folding max |h| into the layer's slot
+        MOLCLR_TRY(molclr_gemm_f32_bplanes_max((const float*)h, e->weight_planes[l], (float*)xw, N,
+                                               D, D, D, D, MOLCLR_EPI_NONE, nullptr, nullptr, 0,
+                                               F(lay.hmax[l]), nullptr, nullptr, nullptr, kws,
+                                               kws_bytes, stream));
+      else
+        MOLCLR_TRY(molclr_gemm_f32_bplanes((const float*)h, e->weight_planes[l], (float*)xw, N, D,
+                                           D, D, D, 0, MOLCLR_EPI_NONE, nullptr, nullptr, 0, kws,
+                                           kws_bytes, stream));
+      MOLCLR_TRY(molclr_gcn_aggregate_fwd((const float*)xw, g->rowptr, g->col, g->ecode, g->nbr,
+                                          e->edge_embedding1[l], e->edge_embedding2[l], e->bias[l],
+                                          (float*)z, N, D, stream));
+    }
     MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
-                          e->bn_running_var[l], e->bn_num_batches_tracked[l], y, A + lay.mean[l],
-                          A + lay.invstd[l], D, MOLCLR_DTYPE_F32, e->momentum, e->eps,
-                          e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes, stream));
+                          e->bn_running_var[l], e->bn_num_batches_tracked[l], y, F(lay.mean[l]),
+                          F(lay.invstd[l]), D, e->dtype, e->momentum, e->eps, e->training,
+                          last ? 0 : 1, drop.at(l), kws, kws_bytes, stream));
     h = y;
   }
   return MOLCLR_OK;
@@ -750,7 +788,7 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
 
 MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
                                       const molclr_gcn_encoder_grads* gr, const int64_t* x,
-                                      const molclr_device_graph* g, const float* dh_out,
+                                      const molclr_device_graph* g, const void* dh_out,
                                       const void* arena, size_t arena_bytes, void* workspace,
                                       size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_TRY(check_gcn(e, g));
@@ -762,56 +800,74 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
   SegRows seg;
   MOLCLR_TRY(graph_segments(g, &g->num_nodes, seg));
   MOLCLR_REQUIRE(x && dh_out && arena, "gcn_encoder_bwd: null pointer");
-  const GcnArena lay(L, N, D);
+  const bool bf = e->dtype == MOLCLR_DTYPE_BF16;
+  const size_t es = elem_bytes(e->dtype);
+  const GcnArena lay(L, N, D, es);
   MOLCLR_REQUIRE_WS(arena_bytes, lay.total);
-  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_encoder_workspace_bytes(L, N, D));
-  const float* A = (const float*)arena;
-  float* S = (float*)workspace;
-  float* dxw = S;
-  float* dz = S + N * D;
-  float* dh = S + 2 * N * D;
+  MOLCLR_REQUIRE_WS(workspace_bytes, molclr_gcn_encoder_workspace_bytes_dtype(L, N, D, e->dtype));
+  const char* A = (const char*)arena;
+  auto F = [&](size_t off) { return (const float*)(A + off); };
+  char* S = (char*)workspace;
+  void* dxw = S;
+  void* dz = S + (size_t)N * D * es;
+  void* dh = S + 2 * (size_t)N * D * es;
   // h3: dxw's row maxima and max slot
-  float* rdxw = (float*)((char*)workspace +
-                         molclr::align_up(gcn_scratch_floats(N, D) * sizeof(float), 256));
+  float* rdxw = (float*)(S + molclr::align_up(gcn_scratch_bytes(N, D, es), 256));
   float* sdxw = (float*)((char*)rdxw + molclr::align_up((size_t)N * sizeof(float), 256));
   void* kws = (char*)rdxw + gcn_h3_bytes(N);
-  const size_t kws_bytes = gcn_kernels_ws(N, D);
+  const size_t kws_bytes = gcn_kernels_ws(N, D, e->dtype);
   const bool h3 = e->fp32_gemm == 1;
   CallDrop drop(e->training, e->drop_ratio, A + lay.dropkey);  // the forward's key
 
-  const float* dy = dh_out;
+  const void* dy = dh_out;
   for (int l = L - 1; l >= 0; --l) {
-    const float* z = A + lay.z[l];
-    const float* xin = l == 0 ? A + lay.h0 : A + lay.h[l - 1];
+    const void* z = A + lay.z[l];
+    const void* xin = l == 0 ? A + lay.h0 : A + lay.h[l - 1];
     const bool last = l == L - 1;
     MOLCLR_REQUIRE(gr->bn_weight[l] && gr->bn_bias[l], "gcn_encoder_bwd: BatchNorm grads needed");
-    MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], A + lay.mean[l],
-                          A + lay.invstd[l], dz, gr->bn_weight[l], gr->bn_bias[l], D,
-                          MOLCLR_DTYPE_F32, last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws,
-                          kws_bytes, stream));
+    MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
+                          F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D, e->dtype,
+                          last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws, kws_bytes, stream));
     // ops._GCNConv.backward order: aggregation (dxw, edge tables, bias), dW, dx
-    MOLCLR_TRY(molclr_gcn_aggregate_bwd(dz, g->rowptr_t, g->col_t, g->nbr_t, g->ecount, dxw,
-                                        gr->edge_embedding1[l], gr->edge_embedding2[l],
-                                        gr->bias[l], N, D, 1, kws, kws_bytes, stream));
-    if (h3) {
-      // ops._GCNConv's h3 backward: dxw's row maxima / max, dW = x^T dxw
-      // (per-tensor scales), dx = dxw W^T (row-wise)
-      MOLCLR_TRY(molclr_absmax_rows_f32(dxw, N, D, D, rdxw, sdxw, 0, stream));
+    if (bf) {
+      MOLCLR_TRY(molclr_gcn_aggregate_bwd_bf16((const uint16_t*)dz, g->rowptr_t, g->col_t,
+                                               g->nbr_t, g->ecount, (uint16_t*)dxw,
+                                               gr->edge_embedding1[l], gr->edge_embedding2[l],
+                                               gr->bias[l], N, D, 1, kws, kws_bytes, stream));
+      // dW [in, out] += x^T dxw: x in the dy slot, dxw in the x slot, no bias sum
       if (gr->weight[l])
-        MOLCLR_TRY(molclr_linear_wgrad_h3(xin, A + lay.hmax[l], dxw, sdxw, gr->weight[l], nullptr,
-                                          N, D, D, D, D, 1, kws, kws_bytes, stream));
-      MOLCLR_TRY(molclr_gemm_f32_h3(dxw, rdxw, 1, e->weight_planes_t[l], dh, N, D, D, D, D,
-                                    MOLCLR_EPI_NONE, nullptr, nullptr, 0, nullptr, nullptr,
-                                    nullptr, nullptr, stream));
+        MOLCLR_TRY(molclr_linear_wgrad_bf16((const uint16_t*)xin, (const uint16_t*)dxw,
+                                            gr->weight[l], nullptr, N, D, D, D, D, 1, kws,
+                                            kws_bytes, stream));
+      MOLCLR_TRY(molclr_gemm_bf16((const uint16_t*)dxw, e->weight_planes_t[l], (uint16_t*)dh, N, D,
+                                  D, D, D, MOLCLR_EPI_NONE, nullptr, nullptr, 0, stream));
     } else {
-      if (gr->weight[l])  // dW [in, out] = x^T dxw
-        MOLCLR_TRY(molclr_gemm_f32(xin, dxw, gr->weight[l], D, D, N, D, D, D, 1, 1,
-                                   MOLCLR_EPI_NONE | MOLCLR_EPI_ACCUMULATE, nullptr, nullptr, 0,
-                                   kws, kws_bytes, stream));
-      // dx = dxw W^T  (ops.gemm_w(dxw, W, N, D, D, D, D, False, False))
-      MOLCLR_TRY(molclr_gemm_f32_bplanes(dxw, e->weight_planes_t[l], dh, N, D, D, D, D, 0,
-                                         MOLCLR_EPI_NONE, nullptr, nullptr, 0, kws, kws_bytes,
-                                         stream));
+      const float* fxin = (const float*)xin;
+      float *fdxw = (float*)dxw, *fdh = (float*)dh;
+      MOLCLR_TRY(molclr_gcn_aggregate_bwd((const float*)dz, g->rowptr_t, g->col_t, g->nbr_t,
+                                          g->ecount, fdxw, gr->edge_embedding1[l],
+                                          gr->edge_embedding2[l], gr->bias[l], N, D, 1, kws,
+                                          kws_bytes, stream));
+      if (h3) {
+        // ops._GCNConv's h3 backward: dxw's row maxima / max, dW = x^T dxw
+        // (per-tensor scales), dx = dxw W^T (row-wise)
+        MOLCLR_TRY(molclr_absmax_rows_f32(fdxw, N, D, D, rdxw, sdxw, 0, stream));
+        if (gr->weight[l])
+          MOLCLR_TRY(molclr_linear_wgrad_h3(fxin, F(lay.hmax[l]), fdxw, sdxw, gr->weight[l],
+                                            nullptr, N, D, D, D, D, 1, kws, kws_bytes, stream));
+        MOLCLR_TRY(molclr_gemm_f32_h3(fdxw, rdxw, 1, e->weight_planes_t[l], fdh, N, D, D, D, D,
+                                      MOLCLR_EPI_NONE, nullptr, nullptr, 0, nullptr, nullptr,
+                                      nullptr, nullptr, stream));
+      } else {
+        if (gr->weight[l])  // dW [in, out] = x^T dxw
+          MOLCLR_TRY(molclr_gemm_f32(fxin, fdxw, gr->weight[l], D, D, N, D, D, D, 1, 1,
+                                     MOLCLR_EPI_NONE | MOLCLR_EPI_ACCUMULATE, nullptr, nullptr, 0,
+                                     kws, kws_bytes, stream));
+        // dx = dxw W^T  (ops.gemm_w(dxw, W, N, D, D, D, D, False, False))
+        MOLCLR_TRY(molclr_gemm_f32_bplanes(fdxw, e->weight_planes_t[l], fdh, N, D, D, D, D, 0,
+                                           MOLCLR_EPI_NONE, nullptr, nullptr, 0, kws, kws_bytes,
+                                           stream));
+      }
     }
     MOLCLR_TRY(record_done(gr->layer_done[l], stream));
     dy = dh;
@@ -819,8 +875,13 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
   if (gr->x_embedding1 || gr->x_embedding2) {
     MOLCLR_REQUIRE(gr->x_embedding1 && gr->x_embedding2,
                    "gcn_encoder_bwd: both atom-embedding grads or neither");
-    MOLCLR_TRY(molclr_atom_embed_bwd(x, dh, gr->x_embedding1, gr->x_embedding2, N, D, e->n_atom,
-                                     e->n_chiral, 1, kws, kws_bytes, stream));
+    if (bf)
+      MOLCLR_TRY(molclr_atom_embed_bwd_bf16(x, (const uint16_t*)dh, gr->x_embedding1,
+                                            gr->x_embedding2, N, D, e->n_atom, e->n_chiral, 1, kws,
+                                            kws_bytes, stream));
+    else
+      MOLCLR_TRY(molclr_atom_embed_bwd(x, (const float*)dh, gr->x_embedding1, gr->x_embedding2, N,
+                                       D, e->n_atom, e->n_chiral, 1, kws, kws_bytes, stream));
   }
   MOLCLR_TRY(record_done(gr->embed_done, stream));
   return MOLCLR_OK;

@@ -43,8 +43,10 @@ int64_t band_parts_bound(int64_t rows, int band, int nseg) {
 // ---------------------------------------------------------------------------
 // column sums
 // ---------------------------------------------------------------------------
-__global__ void k_colsum_partial(const float4* __restrict__ X, int64_t rows, int d4, int64_t ld4,
-                                 int band, int64_t rows_per_part, float4* __restrict__ partial) {
+template <typename St = StF32>
+__global__ void k_colsum_partial(const typename St::T* __restrict__ X, int64_t rows, int d4,
+                                 int64_t ld4, int band, int64_t rows_per_part,
+                                 float4* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) float4 red[];  // [band][d4]
   const int tid = threadIdx.x;
   const bool live = tid < band * d4;
@@ -55,7 +57,7 @@ __global__ void k_colsum_partial(const float4* __restrict__ X, int64_t rows, int
   float4 acc = f4zero();
   if (live) {
 #pragma unroll 4
-    for (int64_t i = beg + r; i < end; i += band) acc = f4add(acc, X[i * ld4 + c]);
+    for (int64_t i = beg + r; i < end; i += band) acc = f4add(acc, St::ld(X, i * ld4 + c));
   }
   if (live) red[r * d4 + c] = acc;
   __syncthreads();
@@ -812,8 +814,8 @@ size_t molclr_colsum_ws(int64_t rows, int64_t cols) {
   return (size_t)band_parts(rows, b.band) * cols * sizeof(float) + 256;
 }
 
-int molclr_colsum_impl(const float* X, float* out, int64_t rows, int64_t cols, int64_t ld,
-                       int accumulate, molclr::Workspace& w, hipStream_t s) {
+int molclr_colsum_impl(const void* X, int dtype, float* out, int64_t rows, int64_t cols,
+                       int64_t ld, int accumulate, molclr::Workspace& w, hipStream_t s) {
   MOLCLR_REQUIRE(molclr::band_dim_ok(cols),
                  "colsum: cols %lld must be a multiple of 4 in [4, %lld]", (long long)cols,
                  (long long)molclr::kBandMaxDim);
@@ -827,8 +829,12 @@ int molclr_colsum_impl(const float* X, float* out, int64_t rows, int64_t cols, i
   }
   int64_t rpp = molclr::ceil_div(rows > 0 ? rows : 1, P);
   size_t lds = (size_t)b.band * b.d4 * sizeof(float4);
-  hipLaunchKernelGGL(k_colsum_partial, dim3(P), dim3(b.threads), lds, s, (const float4*)X, rows,
-                     b.d4, ld / 4, b.band, rpp, (float4*)partial);
+  if (dtype == MOLCLR_DTYPE_BF16)
+    hipLaunchKernelGGL(k_colsum_partial<StBF16>, dim3(P), dim3(b.threads), lds, s,
+                       (const uint16_t*)X, rows, b.d4, ld / 4, b.band, rpp, (float4*)partial);
+  else
+    hipLaunchKernelGGL(k_colsum_partial<StF32>, dim3(P), dim3(b.threads), lds, s, (const float*)X,
+                       rows, b.d4, ld / 4, b.band, rpp, (float4*)partial);
   hipLaunchKernelGGL(k_colsum_final, dim3(molclr::ceil_div(cols, kRedCols)), dim3(kRedCols * kRedLanes), 0, s, partial, P,
                      cols, out, accumulate);
   MOLCLR_LAUNCHED();
@@ -847,7 +853,8 @@ MOLCLR_API int molclr_colsum_f32(const float* X, float* out, int64_t rows, int64
                  (long long)molclr::kBandMaxDim);
   MOLCLR_REQUIRE_WS(workspace_bytes, molclr_colsum_ws(rows, cols));
   molclr::Workspace w(workspace, workspace_bytes);
-  return molclr_colsum_impl(X, out, rows, cols, ld, accumulate, w, molclr::as_stream(stream));
+  return molclr_colsum_impl(X, MOLCLR_DTYPE_F32, out, rows, cols, ld, accumulate, w,
+                            molclr::as_stream(stream));
 }
 
 namespace {

@@ -46,7 +46,7 @@ class Encoder(nn.Module):
     (models/ginet_molclr.py:50-117, models/gcn_molclr.py:94-158) and the
     projection head's forward of the two pre-training models."""
 
-    precision = 'fp32'  # GINet sets 'fp32' | 'bf16' per instance
+    precision = 'fp32'  # GINet and GCN set 'fp32' | 'bf16' per instance
 
     # F.pad of each _layer_params entry in units of the pad p; None: not padded
     _LAYER_PADS: tuple = ()

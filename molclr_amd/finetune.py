@@ -26,7 +26,9 @@ training step and the evaluation passes are replayed from HIP graphs
 one RuntimeWarning.  The motif model is taken with ``hip_graph_motif: True``
 (default False) next to ``hip_graph: True``: the batch's items from
 molclr_amd.motifs.motif_batch are then staged next to the batch; without that
-key it warns and trains eagerly.  Invalid inputs (graph indices, atom features, class
+key it warns and trains eagerly.  ``model_type: gcn`` with ``fp16_precision:
+True`` trains in fp32 after a RuntimeWarning unless ``gcn_bf16: True`` (default
+False) is set too, which builds the GCN with ``precision='bf16'``.  Invalid inputs (graph indices, atom features, class
 labels, motif indices) raise at the next log step (``check_inputs``), as in
 molclr_amd.molclr.
 """
@@ -169,7 +171,9 @@ class FineTune(object):
             model = GINet(task, **mcfg).to(self.device)
         elif self.config['model_type'] == 'gcn':
             from .gcn_finetune import GCN
-            if self.config.get('fp16_precision', False):
+            if self.config.get('fp16_precision', False) and self.config.get('gcn_bf16', False):
+                mcfg['precision'] = 'bf16'  # opt-in: the GCN's bf16 storage path
+            elif self.config.get('fp16_precision', False):
                 warnings.warn("fp16_precision: True with model_type: gcn -- the GCN encoder has "
                               "no reduced-precision path; training in fp32", RuntimeWarning,
                               stacklevel=2)

@@ -20,10 +20,11 @@ class GCN(FinetuneReadout, gcn_molclr.GCN):
     """models/gcn_finetune.py:94-174."""
 
     def __init__(self, task='classification', num_layer=5, emb_dim=300, feat_dim=256,
-                 drop_ratio=0, pool='mean'):
+                 drop_ratio=0, pool='mean', precision='fp32'):
         # The parent's __init__ is NOT called (it would create out_lin, see
         # ginet_finetune.GINet).
         nn.Module.__init__(self)
+        self.precision = gcn_molclr.check_precision(precision)
         self.task = task
         out_dim = task_out_dim(task)
         self._init_encoder(num_layer, emb_dim, feat_dim, drop_ratio, pool)

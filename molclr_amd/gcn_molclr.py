@@ -22,6 +22,7 @@ from . import ops
 from .data import DeviceGraph
 from .encoder import (Encoder, num_atom_type, num_bond_direction,  # noqa: F401
                       num_bond_type, num_chirality_tag)
+from .ginet_molclr import check_precision
 
 
 class GCNConv(nn.Module):
@@ -63,8 +64,14 @@ class GCNConv(nn.Module):
 class GCN(Encoder):
     """models/gcn_molclr.py:94-158; constructor and forward plumbing: Encoder."""
 
-    def __init__(self, num_layer=5, emb_dim=300, feat_dim=256, drop_ratio=0, pool='mean'):
+    def __init__(self, num_layer=5, emb_dim=300, feat_dim=256, drop_ratio=0, pool='mean',
+                 precision='fp32'):
         super().__init__()
+        # 'bf16': the reference's fp16_precision switch for the GCN
+        # (molclr.py:16-24,93-96): bf16 node features, x W and dxw W^T as bf16
+        # MFMA products with fp32 accumulation; fp32 master weights, edge
+        # scalars, bias, BatchNorm statistics, pooled features, heads, NT-Xent
+        self.precision = check_precision(precision)
         self._init_encoder(num_layer, emb_dim, feat_dim, drop_ratio, pool)
         self._init_projection_head()
 
@@ -77,7 +84,7 @@ class GCN(Encoder):
         return GCNConv(emb_dim, aggr="add")
 
     def _pad_multiple(self):
-        return 4
+        return 8 if self.precision == 'bf16' else 4
 
     def _layer_params(self, g, bn):
         return [g.weight, g.bias, g.edge_embedding1.weight, g.edge_embedding2.weight,
@@ -88,7 +95,7 @@ class GCN(Encoder):
 
     def _executor(self, x, graph, bns, params):
         return ops.gcn_encoder(x, graph, bns, params, drop_ratio=self.drop_ratio,
-                               drop_state=self._dropout_state())
+                               drop_state=self._dropout_state(), precision=self.precision)
 
     def _layer_step(self, graph):
         return lambda l, h: self.gnns[l].conv(h, graph)

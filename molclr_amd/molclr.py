@@ -124,17 +124,22 @@ class MolCLR(object):
             model = GINet(**self.config["model"], precision=prec).to(self.device)
         elif self.config['model_type'] == 'gcn':
             from .gcn_molclr import GCN
-            if self.config.get('fp16_precision', False):
+            prec = 'fp32'
+            if self.config.get('fp16_precision', False) and self.config.get('gcn_bf16', False):
+                # gcn_bf16: True opts in to the GCN's bf16 storage path, the
+                # reference's apex run of this configuration
+                # (molclr.py:16-24,93-96)
+                prec = 'bf16'
+            elif self.config.get('fp16_precision', False):
                 # The reference's switch only takes effect with apex installed
                 # (molclr.py:14-22,93-96,121-125); without it the reference
-                # prints a notice and trains in fp32.  The GCN kernels have no
-                # reduced-precision storage path, so this is the reference's
-                # no-apex behaviour: a warning, then fp32
+                # prints a notice and trains in fp32.  Without gcn_bf16 this is
+                # the reference's no-apex behaviour: a warning, then fp32
                 warnings.warn("fp16_precision: True with model_type: gcn -- the GCN encoder has "
                               "no reduced-precision path; training in fp32 (the reference's "
                               "behaviour without apex, molclr.py:14-22,93-96)", RuntimeWarning,
                               stacklevel=2)
-            model = GCN(**self.config["model"]).to(self.device)
+            model = GCN(**self.config["model"], precision=prec).to(self.device)
         else:
             raise ValueError('Undefined GNN model.')
         return self._load_pre_trained_weights(model)

@@ -1118,6 +1118,7 @@ class _EncoderKind:
     symbol: str  # C prefix of _fwd, _bwd, _arena_bytes, _workspace_bytes
     layer_params: tuple  # per-layer parameter fields, in the order of params
     sized_by_dtype: bool  # the size queries take the dtype after (L, N, D)
+    size_suffix: str  # ... and are named <symbol>_arena_bytes<suffix>, _workspace_bytes<suffix>
     fill: object  # (enc, layers, N, D, dtype): the GEMM form and the weight planes
     account: object  # (enc, graph, N, D, dtype, backward): one layer's KernelTimer work
 
@@ -1150,7 +1151,10 @@ def _gin_account(enc, graph, N, D, dtype, backward):
 
 
 def _gcn_fill(enc, layers, N, D, dtype):
-    h3 = gcn_h3_ok(N, D)  # the form _GCNConv uses on these shapes
+    enc.dtype = dtype
+    # fp32: the form _GCNConv uses on these shapes; bf16 reads plane 0 of the
+    # plain images (as _gin_fill's), no h3
+    h3 = dtype == _lib.DTYPE_F32 and gcn_h3_ok(N, D)
     enc.fp32_gemm = int(h3)
     for l, (W, *_) in enumerate(layers):
         # the planes (and cache entries) _GCNConv's gemm_w calls use
@@ -1163,14 +1167,16 @@ def _gcn_account(enc, graph, N, D, dtype, backward):
         _TIMER.add("gemm_f32", 2 * 2.0 * N * D * D)
         return
     _TIMER.add("gemm_f32", 2.0 * N * D * D)
+    es = 2 if dtype == _lib.DTYPE_BF16 else 4
     # the GCN scatter-add moves the same compulsory bytes as GINE's
-    _TIMER.add("gcn_aggregate_fwd", gine_aggregate_bytes(N, D, graph.num_edges))
+    _TIMER.add("gcn_aggregate_fwd", gine_aggregate_bytes(N, D, graph.num_edges, es))
 
 
 _GIN = _EncoderKind(_lib.GinEncoder, _lib.GinEncoderGrads, "molclr_gin_encoder",
-                    _lib.GIN_LAYER_PARAMS, True, _gin_fill, _gin_account)
+                    _lib.GIN_LAYER_PARAMS, True, "", _gin_fill, _gin_account)
+# (the three-argument GCN queries are the fp32 sizes)
 _GCN = _EncoderKind(_lib.GcnEncoder, _lib.GcnEncoderGrads, "molclr_gcn_encoder",
-                    _lib.GCN_LAYER_PARAMS, False, _gcn_fill, _gcn_account)
+                    _lib.GCN_LAYER_PARAMS, True, "_dtype", _gcn_fill, _gcn_account)
 GIN_PARAMS_PER_LAYER = len(_GIN.layer_params)
 GCN_PARAMS_PER_LAYER = len(_GCN.layer_params)
 
@@ -1220,9 +1226,9 @@ class _Encoder(torch.autograd.Function):
             ctx.drop_state = state  # the struct holds its address
         dev = x_idx.device
         sizes = (L, N, D, dtype) if kind.sized_by_dtype else (L, N, D)
-        arena_bytes = _wsq(kind.symbol + "_arena_bytes", *sizes)
+        arena_bytes = _wsq(kind.symbol + "_arena_bytes" + kind.size_suffix, *sizes)
         arena = torch.empty(max(arena_bytes // 4, 1), dtype=torch.float32, device=dev)
-        ws_bytes = _wsq(kind.symbol + "_workspace_bytes", *sizes)
+        ws_bytes = _wsq(kind.symbol + "_workspace_bytes" + kind.size_suffix, *sizes)
         ws = _ws(ws_bytes, dev)
         h = torch.empty(N, D, dtype=TORCH_DTYPE[dtype], device=dev)
         gc = graph.cstruct()
@@ -1261,7 +1267,7 @@ class _Encoder(torch.autograd.Function):
             field = getattr(gr, nm)
             for l in range(L):
                 field[l] = bufs[2 + n * l + j].data_ptr()
-        ws_bytes = _wsq(kind.symbol + "_workspace_bytes", *ctx.sizes)
+        ws_bytes = _wsq(kind.symbol + "_workspace_bytes" + kind.size_suffix, *ctx.sizes)
         ws = _ws(ws_bytes, dh.device)
         gc = ctx.graph.cstruct()
         hook = _grad_events(gr, L, owned)
@@ -1277,11 +1283,14 @@ class _Encoder(torch.autograd.Function):
         return (None, None, None, None, None, None, *ret)
 
 
-def gcn_encoder(x_idx, graph, bns, params, drop_ratio: float = 0.0, drop_state=None):
+def gcn_encoder(x_idx, graph, bns, params, drop_ratio: float = 0.0, drop_state=None,
+                precision: str = "fp32"):
     """GCN.encode through the encoder executor (see _Encoder).  drop_ratio in
     (0, 1) while training: dropout after every BatchNorm, its masks drawn from
-    drop_state (int64 [seed, call counter] on the device)."""
-    return _Encoder.apply(_GCN, x_idx, graph, bns, _lib.DTYPE_F32, (drop_ratio, drop_state),
+    drop_state (int64 [seed, call counter] on the device).  precision "bf16":
+    bf16 node features and bf16 MFMA products (emb_dim % 8 == 0), bf16 node
+    embeddings returned; as gin_encoder's."""
+    return _Encoder.apply(_GCN, x_idx, graph, bns, DTYPES[precision], (drop_ratio, drop_state),
                           *params)
 
 
