@@ -706,6 +706,42 @@ int molclr_batchnorm_seg_bwd_max(const float* dy, const float* z, const float* g
                                  int accumulate, float* rowmax, float* slot, void* workspace,
                                  size_t workspace_bytes, molclr_stream_t stream);
 
+/* The backward through frozen statistics: save_mean / save_invstd are the ones
+ * an eval-mode forward (training = 0) saved, i.e. the running statistics.
+ * dz = gamma * invstd * g does not depend on the column sums, so one pass over
+ * dy and z stores dz and leaves the partial sums of dgamma / dbeta (same
+ * partitions, same fixed order as the training-mode backward; no atomics).
+ * Arguments, segment plans, rowmax / slot and workspace queries are those of
+ * molclr_batchnorm_bwd / _seg_bwd / _seg_bwd_dev / _seg_bwd_max.  A segment
+ * of one row is legal. */
+int molclr_batchnorm_bwd_frozen(const float* dy, const float* z, const float* gamma,
+                                const float* beta, const float* save_mean,
+                                const float* save_invstd, float* dz, float* dgamma,
+                                float* dbeta, int64_t rows, int64_t dim, int relu,
+                                int accumulate, void* workspace, size_t workspace_bytes,
+                                molclr_stream_t stream);
+int molclr_batchnorm_seg_bwd_frozen(const void* dy, const void* z, const float* gamma,
+                                    const float* beta, const float* save_mean,
+                                    const float* save_invstd, void* dz, float* dgamma,
+                                    float* dbeta, int nseg, const int64_t* seg_rows, int64_t dim,
+                                    int dtype, int relu, int accumulate, void* workspace,
+                                    size_t workspace_bytes, molclr_stream_t stream);
+int molclr_batchnorm_seg_bwd_frozen_dev(const void* dy, const void* z, const float* gamma,
+                                        const float* beta, const float* save_mean,
+                                        const float* save_invstd, void* dz, float* dgamma,
+                                        float* dbeta, int nseg, const int64_t* seg_rows_dev,
+                                        int64_t rows_cap, int64_t dim, int dtype, int relu,
+                                        int accumulate, float* rowmax, float* slot,
+                                        void* workspace, size_t workspace_bytes,
+                                        molclr_stream_t stream);
+int molclr_batchnorm_seg_bwd_frozen_max(const float* dy, const float* z, const float* gamma,
+                                        const float* beta, const float* save_mean,
+                                        const float* save_invstd, float* dz, float* dgamma,
+                                        float* dbeta, int nseg, const int64_t* seg_rows,
+                                        int64_t dim, int relu, int accumulate, float* rowmax,
+                                        float* slot, void* workspace, size_t workspace_bytes,
+                                        molclr_stream_t stream);
+
 /* Segment pooling over graph_ptr (PyG global_mean_pool / global_add_pool):
  * mode 0 = mean (sum / max(count,1)), 1 = add. */
 int molclr_segment_pool_fwd(const float* h, const int32_t* graph_ptr, float* out,
@@ -853,9 +889,16 @@ int molclr_step_tail(int32_t* step, const float* loss_src, float* loss_dst,
  * arena.  A backward therefore sees its own forward's masks however many
  * forwards ran in between, and a replayed HIP graph draws fresh masks.
  * ------------------------------------------------------------------------ */
+/* The `training` field of both encoder structs. */
+enum {
+  MOLCLR_MODE_EVAL = 0,      /* running statistics, no dropout */
+  MOLCLR_MODE_TRAIN = 1,     /* batch statistics, running statistics updated, dropout */
+  MOLCLR_MODE_FROZEN_BN = 2  /* running statistics, nothing updated
+                              * (num_batches_tracked included), dropout as in training */
+};
 typedef struct molclr_gin_encoder {
   int32_t num_layer;  /* 1 .. MOLCLR_MAX_LAYERS */
-  int32_t training;
+  int32_t training;   /* MOLCLR_MODE_*; the backward runs in every mode */
   int64_t dim;        /* emb_dim, multiple of 4 */
   int64_t n_atom;     /* x_embedding1 rows (119) */
   int64_t n_chiral;   /* x_embedding2 rows (3) */
@@ -969,7 +1012,7 @@ int molclr_gin_encoder_bwd(const molclr_gin_encoder* enc, const molclr_gin_encod
  * weight_planes_t[l] as the B operand of dxw W^T (b_kmajor=0). */
 typedef struct molclr_gcn_encoder {
   int32_t num_layer;
-  int32_t training;
+  int32_t training; /* MOLCLR_MODE_* */
   int64_t dim;
   int64_t n_atom;
   int64_t n_chiral;

@@ -113,6 +113,15 @@ SIGNATURES = {
                                      c_double, c_int, c_int, _P, c_size_t, _P]),
     "molclr_batchnorm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int, c_int,
                                      _P, c_size_t, _P]),
+    "molclr_batchnorm_bwd_frozen": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, c_int,
+                                            c_int, _P, c_size_t, _P]),
+    "molclr_batchnorm_seg_bwd_frozen": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _I64,
+                                                c_int, c_int, c_int, _P, c_size_t, _P]),
+    "molclr_batchnorm_seg_bwd_frozen_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
+                                                    _I64, _I64, c_int, c_int, c_int, _P, _P, _P,
+                                                    c_size_t, _P]),
+    "molclr_batchnorm_seg_bwd_frozen_max": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
+                                                    _I64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "molclr_batchnorm_seg_workspace_bytes": (c_size_t, [c_int, _P, _I64]),
     "molclr_batchnorm_seg_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _I64, c_int,
                                          c_double, c_double, c_int, c_int, _P, c_size_t, _P]),
@@ -224,6 +233,8 @@ NUM_ECOMB = 15  # combined edge-table rows (bond type * 3 + bond dir)
 MAX_LAYERS = 16
 MAX_SEGMENTS = 8
 DTYPE_F32, DTYPE_BF16 = 0, 1
+# the encoder structs' `training` field (MOLCLR_MODE_*)
+MODE_EVAL, MODE_TRAIN, MODE_FROZEN_BN = 0, 1, 2
 STATUS_ATOM_RANGE = 8  # MOLCLR_STATUS_ATOM_RANGE
 STATUS_LABEL_RANGE = 16  # MOLCLR_STATUS_LABEL_RANGE
 STATUS_MOTIF_RANGE = 32  # MOLCLR_STATUS_MOTIF_RANGE

@@ -211,6 +211,15 @@ int batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* gamma, co
                            int relu, int accumulate, float* rowmax, float* slot,
                            const DropArgs& drop, void* workspace, size_t workspace_bytes,
                            hipStream_t s);
+// the backward through frozen statistics (molclr_batchnorm_seg_bwd_frozen*),
+// host- or device-sized segments; drop: the dropout after it (NULL: none)
+int batchnorm_seg_bwd_frozen_drop(const void* dy, const void* z, const float* gamma,
+                                  const float* beta, const float* save_mean,
+                                  const float* save_invstd, void* dz, float* dgamma, float* dbeta,
+                                  int nseg, const int64_t* seg_rows, const int64_t* seg_rows_dev,
+                                  int64_t rows_cap, int64_t D, int dtype, int relu, int accumulate,
+                                  float* rowmax, float* slot, const DropArgs* drop,
+                                  void* workspace, size_t workspace_bytes, hipStream_t s);
 // aggregate.hip: molclr_gine_aggregate_bn_fwd / _bf16, every source element
 // dropped after the BatchNorm (+ReLU), before the bf16 rounding
 int gine_aggregate_bn_fwd_drop(const void* z, const float* coeffs, int relu, int nseg,

@@ -98,8 +98,17 @@ size_t kernels_ws(int64_t N, int64_t D) {
 // backward scratch dh, dz, dagg [N,D] + dz1 [N,2D], in the storage type
 size_t scratch_bytes(int64_t N, int64_t D, size_t es) { return ((size_t)N * D * 3 + (size_t)N * 2 * D) * es; }
 
-// the dropout fields of either encoder struct
+// The `training` field of either encoder struct (MOLCLR_MODE_*): the
+// BatchNorms take batch statistics in MOLCLR_MODE_TRAIN alone, the dropout is
+// drawn in every mode but MOLCLR_MODE_EVAL.
+template <typename E>
+int bn_batch_stats(const E* e) { return e->training == MOLCLR_MODE_TRAIN; }
+
+// the mode and dropout fields of either encoder struct
 int check_drop(const char* who, double drop_ratio, const int64_t* drop_state, int training) {
+  MOLCLR_REQUIRE(training == MOLCLR_MODE_EVAL || training == MOLCLR_MODE_TRAIN ||
+                     training == MOLCLR_MODE_FROZEN_BN,
+                 "%s: training %d (MOLCLR_MODE_*)", who, training);
   MOLCLR_REQUIRE(drop_ratio >= 0.0 && drop_ratio < 1.0, "%s: drop_ratio %g outside [0, 1)", who,
                  drop_ratio);
   MOLCLR_REQUIRE(!(training && drop_ratio > 0.0) || drop_state,
@@ -188,11 +197,17 @@ int seg_bn_coeffs(const SegRows& sg, const void* z, const float* gamma, const fl
                                      stream);
 }
 // rowmax != NULL (fp32): also dz's row maxima and max slot (the h3 scales)
-int seg_bn_bwd(const SegRows& sg, const void* dy, const void* z, const float* gamma,
+// frozen: mean / invstd are the running statistics an eval-mode forward saved
+int seg_bn_bwd(const SegRows& sg, int frozen, const void* dy, const void* z, const float* gamma,
                const float* beta, const float* mean, const float* invstd, void* dz, float* dgamma,
                float* dbeta, int64_t D, int dtype, int relu, int accumulate, float* rowmax,
                float* slot, const DropArgs* drop, void* ws, size_t ws_bytes,
                molclr_stream_t stream) {
+  if (frozen)
+    return molclr::batchnorm_seg_bwd_frozen_drop(dy, z, gamma, beta, mean, invstd, dz, dgamma,
+                                                 dbeta, sg.n, sg.rows, sg.dev, sg.cap, D, dtype,
+                                                 relu, accumulate, rowmax, slot, drop, ws, ws_bytes,
+                                                 molclr::as_stream(stream));
   if (drop)
     return molclr::batchnorm_seg_bwd_drop(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta,
                                           sg.n, sg.rows, sg.dev, sg.cap, D, dtype, relu,
@@ -360,13 +375,13 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
         MOLCLR_TRY(seg_bn_coeffs(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                                  e->bn_running_var[l], e->bn_num_batches_tracked[l],
                                  F(lay.mean[l]), F(lay.invstd[l]), F(lay.coef[l]), D,
-                                 MOLCLR_DTYPE_BF16, e->momentum, e->eps, e->training, kws,
+                                 MOLCLR_DTYPE_BF16, e->momentum, e->eps, bn_batch_stats(e), kws,
                                  kws_bytes, stream));
       else
         MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                               e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
                               F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_BF16, e->momentum,
-                              e->eps, e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes,
+                              e->eps, bn_batch_stats(e), last ? 0 : 1, drop.at(l), kws, kws_bytes,
                               stream));
     } else {
       float *agg = F(lay.agg[l]), *a1 = F(lay.a1[l]), *z = F(lay.z[l]);
@@ -426,13 +441,13 @@ MOLCLR_API int molclr_gin_encoder_fwd(const molclr_gin_encoder* e, const int64_t
         MOLCLR_TRY(seg_bn_coeffs(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                                  e->bn_running_var[l], e->bn_num_batches_tracked[l],
                                  F(lay.mean[l]), F(lay.invstd[l]), F(lay.coef[l]), D,
-                                 MOLCLR_DTYPE_F32, e->momentum, e->eps, e->training, kws, kws_bytes,
+                                 MOLCLR_DTYPE_F32, e->momentum, e->eps, bn_batch_stats(e), kws, kws_bytes,
                                  stream));
       else
         MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                               e->bn_running_var[l], e->bn_num_batches_tracked[l], y,
                               F(lay.mean[l]), F(lay.invstd[l]), D, MOLCLR_DTYPE_F32, e->momentum,
-                              e->eps, e->training, last ? 0 : 1, drop.at(l), kws, kws_bytes,
+                              e->eps, bn_batch_stats(e), last ? 0 : 1, drop.at(l), kws, kws_bytes,
                               stream));
     }
     h = y;
@@ -447,7 +462,6 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
                                       size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_TRY(check_encoder(e, g));
   MOLCLR_REQUIRE(gr, "gin_encoder_bwd: null grads");
-  MOLCLR_REQUIRE(e->training, "gin_encoder_bwd: backward through eval-mode BatchNorm");
   const int L = e->num_layer;
   const int64_t N = g->num_nodes, D = e->dim;
   if (N == 0) return MOLCLR_OK;
@@ -491,12 +505,12 @@ MOLCLR_API int molclr_gin_encoder_bwd(const molclr_gin_encoder* e,
       // dz's row maxima for the h3 products (its max comes from the dz1
       // product's A reads: a max slot here would cost the BatchNorm backward
       // a block barrier)
-      MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
+      MOLCLR_TRY(seg_bn_bwd(seg, !bn_batch_stats(e), dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
                             F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D,
                             MOLCLR_DTYPE_F32, last ? 0 : 1, 1, rdz, nullptr, drop.at(l), kws,
                             kws_bytes, stream));
     } else {
-      MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
+      MOLCLR_TRY(seg_bn_bwd(seg, !bn_batch_stats(e), dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
                             F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D, dt,
                             last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws, kws_bytes, stream));
     }
@@ -779,7 +793,7 @@ MOLCLR_API int molclr_gcn_encoder_fwd(const molclr_gcn_encoder* e, const int64_t
     }
     MOLCLR_TRY(seg_bn_fwd(seg, z, e->bn_weight[l], e->bn_bias[l], e->bn_running_mean[l],
                           e->bn_running_var[l], e->bn_num_batches_tracked[l], y, F(lay.mean[l]),
-                          F(lay.invstd[l]), D, e->dtype, e->momentum, e->eps, e->training,
+                          F(lay.invstd[l]), D, e->dtype, e->momentum, e->eps, bn_batch_stats(e),
                           last ? 0 : 1, drop.at(l), kws, kws_bytes, stream));
     h = y;
   }
@@ -793,7 +807,6 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
                                       size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_TRY(check_gcn(e, g));
   MOLCLR_REQUIRE(gr, "gcn_encoder_bwd: null grads");
-  MOLCLR_REQUIRE(e->training, "gcn_encoder_bwd: backward through eval-mode BatchNorm");
   const int L = e->num_layer;
   const int64_t N = g->num_nodes, D = e->dim;
   if (N == 0) return MOLCLR_OK;
@@ -825,7 +838,7 @@ MOLCLR_API int molclr_gcn_encoder_bwd(const molclr_gcn_encoder* e,
     const void* xin = l == 0 ? A + lay.h0 : A + lay.h[l - 1];
     const bool last = l == L - 1;
     MOLCLR_REQUIRE(gr->bn_weight[l] && gr->bn_bias[l], "gcn_encoder_bwd: BatchNorm grads needed");
-    MOLCLR_TRY(seg_bn_bwd(seg, dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
+    MOLCLR_TRY(seg_bn_bwd(seg, !bn_batch_stats(e), dy, z, e->bn_weight[l], e->bn_bias[l], F(lay.mean[l]),
                           F(lay.invstd[l]), dz, gr->bn_weight[l], gr->bn_bias[l], D, e->dtype,
                           last ? 0 : 1, 1, nullptr, nullptr, drop.at(l), kws, kws_bytes, stream));
     // ops._GCNConv.backward order: aggregation (dxw, edge tables, bias), dW, dx

@@ -642,6 +642,172 @@ __global__ __launch_bounds__(kT) void k_bn_bwd_apply(
   bn_bwd_elem<St, DR>(dy, z, mean, invstd, gamma, beta, k1, k2, dz, t, d4, relu, sg, total4, dr);
 }
 
+// Row maxima as row parts from a band block (k_bn_bwd_frozen): lane tid holds
+// column unit tid - r * d4 of the block's lane-row r, so a row's d4 lanes are
+// contiguous and spread over at most (d4 + 62) / 64 + 1 of the block's waves
+// (bn_row_parts).  part = the lane's wave - the wave of the row's first lane;
+// every (row, part) has one writer, part 0's writer zeroes the parts the row
+// does not reach -- the layout row_max_parts leaves (the row max is the max
+// over the parts).  row = -1 for a lane without a row.  Every lane of the
+// wave must call it.
+__device__ __forceinline__ void band_row_max_parts(float m, int64_t row, int tid, int r, int d4,
+                                                   int64_t rows, float* __restrict__ rowparts,
+                                                   int nparts) {
+  const int lane = tid & 63;
+  const int rr = row >= 0 ? r : -1;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float mv = __shfl_down(m, off, 64);
+    const int rv = __shfl_down(rr, off, 64);
+    if (lane + off < 64 && rv == rr) m = fmaxf(m, mv);
+  }
+  const int rp = __shfl_up(rr, 1, 64);
+  if (rr >= 0 && (lane == 0 || rp != rr)) {
+    const int rs = r * d4;  // the row's first lane in the block
+    const int part = (tid >> 6) - (rs >> 6);
+    rowparts[part * rows + row] = m;
+    if (part == 0)
+      for (int q = ((rs + d4 - 1) >> 6) - (rs >> 6) + 1; q < nparts; ++q)
+        rowparts[q * rows + row] = 0.f;
+  }
+}
+
+// BN backward through frozen statistics (the eval forward's save_mean /
+// save_invstd, k_bn_eval_coeffs): dz = sc * g does not depend on the column
+// sums, so one pass over dy and z stores dz and leaves the partials of Σ g
+// and Σ g * xhat -- k_bn_bwd_partial's partitions, lane rows and row order --
+// for k_bn_bwd_final (dgamma, dbeta).  g = dy behind the ReLU mask and the
+// dropout (DR).  A thread owns U consecutive column units: U = 2 is the bf16
+// form with 16-byte accesses (d4 % 2 == 0, host).  Padding rows of a
+// device-sized plan belong to no partition: every block of the grid, the
+// spare partitions included, zero-fills a strided share of them (and of their
+// row parts) first.  kMax: also dz's row parts and max slot (fp32, U = 1).
+template <typename St, int U, bool kMax, typename DR = NoDrop>
+__global__ void k_bn_bwd_frozen(const typename St::T* __restrict__ dy,
+                                const typename St::T* __restrict__ z,
+                                const float4* __restrict__ mean, const float4* __restrict__ invstd,
+                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                typename St::T* __restrict__ dz, int d4, int band, Segs sg,
+                                int64_t rows, int relu, float4* __restrict__ p1,
+                                float4* __restrict__ p2, float* __restrict__ rowparts, int nparts,
+                                float* __restrict__ slot, DR dr) {
+  extern __shared__ __attribute__((aligned(16))) float4 red[];  // [2][band][d4]
+  const int tid = threadIdx.x;
+  const int du = d4 / U;  // threads per row
+  const bool live = tid < band * du;
+  const int r = live ? tid / du : 0, c = live ? (tid - r * du) * U : 0;
+  if (sg.drows) {  // block-uniform
+    int64_t pad0 = 0;
+    for (int q = 0; q < sg.n; ++q) pad0 += seg_n(sg, q);
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    const int64_t first = (int64_t)blockIdx.x * blockDim.x + tid;
+    for (int64_t t = pad0 * du + first; t < rows * du; t += step) {
+      if constexpr (U == 2) St::st2(dz, t, f4zero(), f4zero());
+      else St::st(dz, t, f4zero());
+    }
+    if constexpr (kMax) {
+      const int64_t npad = rows > pad0 ? rows - pad0 : 0;
+      for (int64_t t = first; t < npad * nparts; t += step)
+        rowparts[(t / npad) * rows + pad0 + t % npad] = 0.f;
+    }
+  }
+  const SegAt at = seg_of_part(sg, blockIdx.x);
+  if (at.s < 0) return;  // spare partition of a device-sized plan (block-uniform)
+  const int s = at.s;
+  const int64_t beg = at.row0 + (blockIdx.x - at.part0) * at.rpp;
+  int64_t end = beg + at.rpp;
+  if (end > at.row1) end = at.row1;
+  float4 s1[U], s2[U], mu[U], is[U], sc[U], sh[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    s1[j] = s2[j] = f4zero();
+    mu[j] = mean[s * d4 + c + j];
+    is[j] = invstd[s * d4 + c + j];
+    bn_coeffs4(gamma, beta, mu[j], is[j], c + j, sc[j], sh[j]);
+  }
+  const Drop<DR> drop(dr);
+  float amax = 0.f;
+  // R rows' loads in flight per round trip; the sums stay in row order.  The
+  // trip count is block-uniform (the row parts need every lane of a wave).
+  constexpr int R = 8 / U;
+  for (int64_t j0 = beg; j0 < end; j0 += R * (int64_t)band) {
+    float4 gv[R][U], xv[R][U];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int64_t i = j0 + r + (int64_t)u * band;
+      const int64_t ii = (live && i < end) ? i : beg;  // beg < end: a row of this partition
+      if constexpr (U == 2) {
+        St::ld2(dy, (ii * d4 + c) / 2, gv[u][0], gv[u][1]);
+        St::ld2(z, (ii * d4 + c) / 2, xv[u][0], xv[u][1]);
+      } else {
+        gv[u][0] = St::ld(dy, ii * d4 + c);
+        xv[u][0] = St::ld(z, ii * d4 + c);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int64_t i = j0 + r + (int64_t)u * band;
+      const bool on = live && i < end;
+      float m = 0.f;
+      if (on) {
+        float4 o[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+          float4 g = gv[u][j];
+          const float4 x = xv[u][j];
+          if (relu) {
+            g.x = bn_apply1(x.x, sc[j].x, sh[j].x) > 0.f ? g.x : 0.f;
+            g.y = bn_apply1(x.y, sc[j].y, sh[j].y) > 0.f ? g.y : 0.f;
+            g.z = bn_apply1(x.z, sc[j].z, sh[j].z) > 0.f ? g.z : 0.f;
+            g.w = bn_apply1(x.w, sc[j].w, sh[j].w) > 0.f ? g.w : 0.f;
+          }
+          if constexpr (DR::kOn) g = drop(g, i, c + j);
+          s1[j] = f4add(s1[j], g);
+          s2[j].x += g.x * ((x.x - mu[j].x) * is[j].x);
+          s2[j].y += g.y * ((x.y - mu[j].y) * is[j].y);
+          s2[j].z += g.z * ((x.z - mu[j].z) * is[j].z);
+          s2[j].w += g.w * ((x.w - mu[j].w) * is[j].w);
+          o[j] = make_float4(sc[j].x * g.x, sc[j].y * g.y, sc[j].z * g.z, sc[j].w * g.w);
+        }
+        if constexpr (U == 2) St::st2(dz, (i * d4 + c) / 2, o[0], o[1]);
+        else St::st(dz, i * d4 + c, o[0]);
+        if constexpr (kMax)
+          m = fmaxf(fmaxf(fabsf(o[0].x), fabsf(o[0].y)), fmaxf(fabsf(o[0].z), fabsf(o[0].w)));
+      }
+      if constexpr (kMax) {
+        // block-uniform: past the partition's last band of rows nobody has one
+        if (j0 + (int64_t)u * band < end) {
+          band_row_max_parts(m, on ? i : -1, tid, r, d4, rows, rowparts, nparts);
+          amax = fmaxf(amax, m);
+        }
+      }
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      red[r * d4 + c + j] = s1[j];
+      red[(band + r) * d4 + c + j] = s2[j];
+    }
+  }
+  __syncthreads();
+  if (live && r == 0) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      float4 a = red[c + j], b = red[band * d4 + c + j];
+      for (int q = 1; q < band; ++q) {
+        a = f4add(a, red[q * d4 + c + j]);
+        b = f4add(b, red[(band + q) * d4 + c + j]);
+      }
+      p1[(int64_t)blockIdx.x * d4 + c + j] = a;
+      p2[(int64_t)blockIdx.x * d4 + c + j] = b;
+    }
+  }
+  if constexpr (kMax) {
+    if (slot != nullptr) absmax_publish(amax, slot);
+  }
+}
+
 
 // ---------------------------------------------------------------------------
 // segment pooling over graph_ptr
@@ -1054,6 +1220,81 @@ int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* bet
   return MOLCLR_OK;
 }
 
+// The backward of the eval forward (running statistics saved per segment):
+// k_bn_bwd_frozen, then k_bn_bwd_final for dgamma / dbeta.  bn_bwd's
+// arguments, plan and workspace layout; a segment of one row is legal.
+template <typename St>
+int bn_bwd_frozen(const void* dyv, const void* zv, const float* gamma, const float* beta,
+                  const float* save_mean, const float* save_invstd, void* dzv, float* dgamma,
+                  float* dbeta, int nseg, const int64_t* seg_rows, int64_t D, int relu,
+                  int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s,
+                  float* rowparts = nullptr, float* slot = nullptr, const int64_t* drows = nullptr,
+                  int64_t cap = 0, const DropArgs* drop = nullptr) {
+  Segs sg;
+  int64_t P = 0, rows = 0;
+  if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
+  MOLCLR_REQUIRE(rows > 0 && dyv && zv && save_mean && save_invstd && dzv,
+                 "batchnorm_bwd_frozen: bad args");
+  for (int q = 0; q < nseg && !drows; ++q)
+    MOLCLR_REQUIRE(seg_rows[q] > 0, "batchnorm_bwd_frozen: empty segment");
+  MOLCLR_REQUIRE_WS(workspace_bytes, bn_ws_bytes(P, D, nseg));
+  MOLCLR_REQUIRE(!rowparts || rows < (1ll << 31), "batchnorm_seg_bwd_frozen_max: too many rows");
+  const auto* dy = static_cast<const typename St::T*>(dyv);
+  const auto* z = static_cast<const typename St::T*>(zv);
+  auto* dz = static_cast<typename St::T*>(dzv);
+  const molclr::Band b = molclr::make_band(D);
+  molclr::Workspace w(workspace, workspace_bytes);
+  float* p1 = w.take<float>(P * D);
+  float* p2 = w.take<float>(P * D);
+  w.take<float>(P);
+  w.take<float>(nseg * D);  // scale
+  w.take<float>(nseg * D);  // shift
+  float* k1 = w.take<float>(nseg * D);
+  float* k2 = w.take<float>(nseg * D);
+  const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
+  auto launch = [&](auto dr) {
+    using DR = decltype(dr);
+    auto go = [&](auto kernel, int threads) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)P), dim3(threads), lds, s, dy, z,
+                         (const float4*)save_mean, (const float4*)save_invstd, gamma, beta, dz,
+                         b.d4, b.band, sg, rows, relu, (float4*)p1, (float4*)p2, rowparts,
+                         bn_row_parts(D), slot, dr);
+    };
+    if constexpr (St::kBytes == 4) {
+      if (rowparts) go(k_bn_bwd_frozen<St, 1, true, DR>, b.threads);
+      else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
+    } else {
+      if (D % 8 == 0) go(k_bn_bwd_frozen<St, 2, false, DR>, (b.band * (b.d4 / 2) + 63) / 64 * 64);
+      else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
+    }
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(molclr::ceil_div(D, kRedCols)),
+                       dim3(kRedCols * kRedLanes), 0, s, p1, p2, sg, D, dgamma, dbeta, k1, k2,
+                       accumulate);
+  };
+  if (drop) launch(*drop);
+  else launch(NoDrop{});
+  MOLCLR_LAUNCHED();
+  return MOLCLR_OK;
+}
+
+// dtype dispatch of bn_bwd_frozen (row maxima are fp32 only)
+int bn_bwd_frozen_any(const char* who, const void* dy, const void* z, const float* gamma,
+                      const float* beta, const float* save_mean, const float* save_invstd,
+                      void* dz, float* dgamma, float* dbeta, int nseg, const int64_t* seg_rows,
+                      const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D, int dtype, int relu,
+                      int accumulate, float* rowmax, float* slot, const DropArgs* drop,
+                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+  MOLCLR_REQUIRE(!rowmax || dtype == MOLCLR_DTYPE_F32, "%s: row maxima are fp32 only", who);
+  if (dtype == MOLCLR_DTYPE_F32)
+    return bn_bwd_frozen<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta,
+                                nseg, seg_rows, D, relu, accumulate, workspace, workspace_bytes, s,
+                                rowmax, slot, seg_rows_dev, rows_cap, drop);
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "%s: dtype %d", who, dtype);
+  return bn_bwd_frozen<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
+                               seg_rows, D, relu, accumulate, workspace, workspace_bytes, s,
+                               nullptr, nullptr, seg_rows_dev, rows_cap, drop);
+}
+
 }  // namespace
 
 // Workspace that covers any split of `rows` rows into <= MOLCLR_MAX_SEGMENTS
@@ -1260,6 +1501,77 @@ int molclr::batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* g
   return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
                         seg_rows, D, relu, accumulate, workspace, workspace_bytes, s, nullptr,
                         nullptr, seg_rows_dev, rows_cap, &drop);
+}
+
+// Backward through frozen statistics: save_mean / save_invstd are the ones an
+// eval-mode forward saved (the running statistics, per segment).  Arguments,
+// plans and workspace of the training-mode entry points of the same names.
+MOLCLR_API int molclr_batchnorm_seg_bwd_frozen(const void* dy, const void* z, const float* gamma,
+                                               const float* beta, const float* save_mean,
+                                               const float* save_invstd, void* dz, float* dgamma,
+                                               float* dbeta, int nseg, const int64_t* seg_rows,
+                                               int64_t D, int dtype, int relu, int accumulate,
+                                               void* workspace, size_t workspace_bytes,
+                                               molclr_stream_t stream) {
+  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen", dy, z, gamma, beta, save_mean, save_invstd,
+                           dz, dgamma, dbeta, nseg, seg_rows, nullptr, 0, D, dtype, relu,
+                           accumulate, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                           molclr::as_stream(stream));
+}
+
+MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_max(const float* dy, const float* z,
+                                                   const float* gamma, const float* beta,
+                                                   const float* save_mean, const float* save_invstd,
+                                                   float* dz, float* dgamma, float* dbeta, int nseg,
+                                                   const int64_t* seg_rows, int64_t D, int relu,
+                                                   int accumulate, float* rowmax, float* slot,
+                                                   void* workspace, size_t workspace_bytes,
+                                                   molclr_stream_t stream) {
+  MOLCLR_REQUIRE(rowmax, "batchnorm_seg_bwd_frozen_max: null rowmax");
+  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen_max", dy, z, gamma, beta, save_mean,
+                           save_invstd, dz, dgamma, dbeta, nseg, seg_rows, nullptr, 0, D,
+                           MOLCLR_DTYPE_F32, relu, accumulate, rowmax, slot, nullptr, workspace,
+                           workspace_bytes, molclr::as_stream(stream));
+}
+
+MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_dev(const void* dy, const void* z, const float* gamma,
+                                                   const float* beta, const float* save_mean,
+                                                   const float* save_invstd, void* dz, float* dgamma,
+                                                   float* dbeta, int nseg,
+                                                   const int64_t* seg_rows_dev, int64_t rows_cap,
+                                                   int64_t D, int dtype, int relu, int accumulate,
+                                                   float* rowmax, float* slot, void* workspace,
+                                                   size_t workspace_bytes, molclr_stream_t stream) {
+  MOLCLR_REQUIRE(seg_rows_dev, "batchnorm_seg_bwd_frozen_dev: null seg_rows_dev");
+  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen_dev", dy, z, gamma, beta, save_mean,
+                           save_invstd, dz, dgamma, dbeta, nseg, nullptr, seg_rows_dev, rows_cap, D,
+                           dtype, relu, accumulate, rowmax, slot, nullptr, workspace,
+                           workspace_bytes, molclr::as_stream(stream));
+}
+
+MOLCLR_API int molclr_batchnorm_bwd_frozen(const float* dy, const float* z, const float* gamma,
+                                           const float* beta, const float* save_mean,
+                                           const float* save_invstd, float* dz, float* dgamma,
+                                           float* dbeta, int64_t rows, int64_t D, int relu,
+                                           int accumulate, void* workspace, size_t workspace_bytes,
+                                           molclr_stream_t stream) {
+  return molclr_batchnorm_seg_bwd_frozen(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma,
+                                         dbeta, 1, &rows, D, MOLCLR_DTYPE_F32, relu, accumulate,
+                                         workspace, workspace_bytes, stream);
+}
+
+// the encoder executors' form: host- or device-sized segments, dropout or none
+int molclr::batchnorm_seg_bwd_frozen_drop(const void* dy, const void* z, const float* gamma,
+                                          const float* beta, const float* save_mean,
+                                          const float* save_invstd, void* dz, float* dgamma,
+                                          float* dbeta, int nseg, const int64_t* seg_rows,
+                                          const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D,
+                                          int dtype, int relu, int accumulate, float* rowmax,
+                                          float* slot, const DropArgs* drop, void* workspace,
+                                          size_t workspace_bytes, hipStream_t s) {
+  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen", dy, z, gamma, beta, save_mean, save_invstd,
+                           dz, dgamma, dbeta, nseg, seg_rows, seg_rows_dev, rows_cap, D, dtype,
+                           relu, accumulate, rowmax, slot, drop, workspace, workspace_bytes, s);
 }
 
 MOLCLR_API int molclr_batchnorm_fwd(const float* z, const float* gamma, const float* beta,

@@ -124,6 +124,34 @@ class Encoder(nn.Module):
     # the executor's kernels); else op by op.
     use_executor = True
 
+    # Frozen BatchNorm: every BatchNorm1d of the encoder stays in eval mode
+    # (running statistics, nothing updated) whatever train() is called with, so
+    # a trainer's per-epoch model.train() does not undo it; the dropout still
+    # follows the model's own flag.  Putting the BatchNorm modules into eval
+    # mode by hand gives the same step until the next train() call.
+    _freeze_bn = False
+
+    @property
+    def freeze_bn(self) -> bool:
+        return self._freeze_bn
+
+    @freeze_bn.setter
+    def freeze_bn(self, value):
+        self._freeze_bn = bool(value)
+        self.train(self.training)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if self._freeze_bn:
+            for bn in self.batch_norms:
+                bn.eval()
+        return self
+
+    def bn_frozen(self) -> bool:
+        """Whether this forward differentiates through running statistics
+        while the model trains (the executor's MODE_FROZEN_BN)."""
+        return self.training and not any(bn.training for bn in self.batch_norms)
+
     def _executor_ok(self) -> bool:
         # any emb_dim: the executor runs on the width padded to the kernels'
         # multiple (_dim_pad) with zero columns

@@ -28,7 +28,9 @@ one RuntimeWarning.  The motif model is taken with ``hip_graph_motif: True``
 molclr_amd.motifs.motif_batch are then staged next to the batch; without that
 key it warns and trains eagerly.  ``model_type: gcn`` with ``fp16_precision:
 True`` trains in fp32 after a RuntimeWarning unless ``gcn_bf16: True`` (default
-False) is set too, which builds the GCN with ``precision='bf16'``.  Invalid inputs (graph indices, atom features, class
+False) is set too, which builds the GCN with ``precision='bf16'``.  ``freeze_bn:
+True`` (default False) keeps every BatchNorm of the encoder on its running
+statistics for the whole run (``model.freeze_bn``).  Invalid inputs (graph indices, atom features, class
 labels, motif indices) raise at the next log step (``check_inputs``), as in
 molclr_amd.molclr.
 """
@@ -163,6 +165,15 @@ class FineTune(object):
 
     # -- model and optimizer --------------------------------------------------
     def build_model(self):
+        model = self._build_model()
+        # freeze_bn: True (default off) -- every BatchNorm of the encoder on its
+        # running statistics for the whole run (model.freeze_bn: model.train()
+        # leaves them in eval mode); dropout and every other layer train on
+        if self.config.get('freeze_bn', False):
+            model.freeze_bn = True
+        return model
+
+    def _build_model(self):
         task, mcfg = self.task, dict(self.config['model'])
         if self.config['model_type'] == 'gin':
             from .ginet_finetune import GINet

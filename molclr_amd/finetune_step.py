@@ -366,10 +366,24 @@ class _CapturedTask:
         # a capture only records: the cached images must be regenerated by the
         # next eager use as well
         ops.bump_param_generation()
-        return _Captured(graph, g, keep)
+        ent = _Captured(graph, g, keep)
+        ent.bn_mode = self._bn_mode()
+        return ent
+
+    def _bn_mode(self) -> tuple:
+        """What a capture is valid for besides its capacities: the model's
+        training flag (the dropout) and each BatchNorm's (batch or running
+        statistics) -- the recorded kernels differ."""
+        return (bool(self.model.training),) + tuple(bool(bn.training)
+                                                    for bn in self.model.batch_norms)
 
     def _replay(self, data, items=None):
         ent, fresh = self._entry(data, items)
+        if ent.bn_mode != self._bn_mode():
+            raise RuntimeError(
+                f"{type(self).__name__}: the model's BatchNorm / training mode changed after "
+                "this bucket was captured (freeze_bn or a BatchNorm's train() / eval()); "
+                "close() the captured graphs and capture again")
         if not fresh:
             self._stage(ent.graph, data, items)
             for opt in self._optimizers():

@@ -95,7 +95,8 @@ class GCN(Encoder):
 
     def _executor(self, x, graph, bns, params):
         return ops.gcn_encoder(x, graph, bns, params, drop_ratio=self.drop_ratio,
-                               drop_state=self._dropout_state(), precision=self.precision)
+                               drop_state=self._dropout_state(), precision=self.precision,
+                               drop_training=self.training)
 
     def _layer_step(self, graph):
         return lambda l, h: self.gnns[l].conv(h, graph)

@@ -89,7 +89,8 @@ class GINet(Encoder):
 
     def _executor(self, x, graph, bns, params):
         return ops.gin_encoder(x, graph, bns, params, self.precision,
-                               drop_ratio=self.drop_ratio, drop_state=self._dropout_state())
+                               drop_ratio=self.drop_ratio, drop_state=self._dropout_state(),
+                               drop_training=self.training)
 
     def _layer_step(self, graph):
         # per-edge embeddings E1[bt] + E2[bd] of every layer, tabulated in one launch

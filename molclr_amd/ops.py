@@ -748,10 +748,6 @@ class _BatchNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if not ctx.training:
-            raise NotImplementedError(
-                "molclr_amd: backward through eval-mode BatchNorm is not supported "
-                "(the reference only evaluates under torch.no_grad, molclr.py:162)")
         z, gamma, beta, save_mean, save_invstd = ctx.saved_tensors
         dy = _c(dy)
         N, D = z.shape
@@ -764,7 +760,9 @@ class _BatchNorm(torch.autograd.Function):
             bb, ab, rb = _grad_sink(None, (D,), z.device)
         ws_bytes = _wsq("molclr_batchnorm_workspace_bytes", N, D)
         ws = _ws(ws_bytes, z.device)
-        _lib.call("molclr_batchnorm_bwd", dy.data_ptr(), z.data_ptr(), _lib.ptr(gamma),
+        # eval mode: save_mean / save_invstd are the running statistics
+        _lib.call("molclr_batchnorm_bwd" if ctx.training else "molclr_batchnorm_bwd_frozen",
+                  dy.data_ptr(), z.data_ptr(), _lib.ptr(gamma),
                   _lib.ptr(beta), save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(),
                   bg.data_ptr(), bb.data_ptr(), N, D, int(ctx.relu), ag, ws.data_ptr(),
                   ws_bytes, _stream(z))
@@ -1186,10 +1184,13 @@ class _Encoder(torch.autograd.Function):
     gcn_molclr.py:140-151) through <kind.symbol>_fwd / _bwd (encoder.hip): the
     same kernels as the per-op path in the same order, one host call each way.
     params: x_embedding1, x_embedding2, then per layer kind.layer_params.
-    drop: None, or (drop_ratio, drop_state) -- dropout after every BatchNorm
-    while training, drop_state the int64 [seed, call counter] on the device
-    (the forward advances the counter; the backward reuses its forward's key,
-    which the forward left in the arena)."""
+    drop: None, or (drop_ratio, drop_state, drop_training) -- dropout after
+    every BatchNorm while drop_training (None: while the BatchNorms train),
+    drop_state the int64 [seed, call counter] on the device (the forward
+    advances the counter; the backward reuses its forward's key, which the
+    forward left in the arena).  The BatchNorms' own flag picks batch or
+    running statistics; with running statistics and dropout the executor runs
+    in _lib.MODE_FROZEN_BN, and the backward runs in every mode."""
 
     @staticmethod
     def forward(ctx, kind: _EncoderKind, x_idx, graph: DeviceGraph, bns, dtype, drop, *params):
@@ -1199,8 +1200,12 @@ class _Encoder(torch.autograd.Function):
         x_idx = _c(x_idx.to(torch.long))
         N = graph.num_nodes
         training = bool(bns[0].training)
+        dropping = training
+        if drop is not None and len(drop) > 2 and drop[2] is not None:
+            dropping = bool(drop[2])
+        mode = _lib.MODE_TRAIN if training else _lib.MODE_FROZEN_BN if dropping else _lib.MODE_EVAL
         enc = kind.struct()
-        enc.num_layer, enc.training, enc.dim = L, int(training), D
+        enc.num_layer, enc.training, enc.dim = L, mode, D
         enc.status = graph.status.data_ptr()  # out-of-vocabulary atoms: MOLCLR_STATUS_ATOM_RANGE
         enc.n_atom, enc.n_chiral = params[0].shape[0], params[1].shape[0]
         enc.momentum, enc.eps = float(bns[0].momentum), float(bns[0].eps)
@@ -1216,8 +1221,8 @@ class _Encoder(torch.autograd.Function):
             nbt = bn.num_batches_tracked
             enc.bn_num_batches_tracked[l] = nbt.data_ptr() if training and nbt is not None else None
         kind.fill(enc, layers, N, D, dtype)
-        if training and drop is not None and drop[0] > 0:
-            ratio, state = drop
+        if dropping and drop is not None and drop[0] > 0:
+            ratio, state = drop[:2]
             if state is None or state.dtype != torch.long or state.numel() != 2 \
                     or state.device != x_idx.device or not state.is_contiguous():
                 raise ValueError("molclr_amd: drop_state must be a contiguous int64 [2] tensor "
@@ -1245,8 +1250,6 @@ class _Encoder(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh):
-        if not ctx.training:
-            raise NotImplementedError("molclr_amd: backward through eval-mode BatchNorm")
         kind = ctx.kind
         dh = _c(dh.to(TORCH_DTYPE[ctx.dtype]))
         params = ctx.params
@@ -1284,23 +1287,27 @@ class _Encoder(torch.autograd.Function):
 
 
 def gcn_encoder(x_idx, graph, bns, params, drop_ratio: float = 0.0, drop_state=None,
-                precision: str = "fp32"):
+                precision: str = "fp32", drop_training=None):
     """GCN.encode through the encoder executor (see _Encoder).  drop_ratio in
     (0, 1) while training: dropout after every BatchNorm, its masks drawn from
     drop_state (int64 [seed, call counter] on the device).  precision "bf16":
     bf16 node features and bf16 MFMA products (emb_dim % 8 == 0), bf16 node
-    embeddings returned; as gin_encoder's."""
-    return _Encoder.apply(_GCN, x_idx, graph, bns, DTYPES[precision], (drop_ratio, drop_state),
-                          *params)
+    embeddings returned; as gin_encoder's.  drop_training: whether the dropout
+    is drawn (None: the BatchNorms' flag); False with BatchNorms in eval mode is
+    plain evaluation, True with them frozen BatchNorm (running statistics,
+    nothing updated, dropout as in training).  Every mode has a backward."""
+    return _Encoder.apply(_GCN, x_idx, graph, bns, DTYPES[precision],
+                          (drop_ratio, drop_state, drop_training), *params)
 
 
 def gin_encoder(x_idx, graph, bns, params, precision: str = "fp32", drop_ratio: float = 0.0,
-                drop_state=None):
+                drop_state=None, drop_training=None):
     """GINet.encode through the encoder executor (see _Encoder); precision
     "bf16" runs the c5 configuration's bf16 storage / bf16 MFMA path and
-    returns bf16 node embeddings.  drop_ratio / drop_state: as gcn_encoder."""
-    return _Encoder.apply(_GIN, x_idx, graph, bns, DTYPES[precision], (drop_ratio, drop_state),
-                          *params)
+    returns bf16 node embeddings.  drop_ratio / drop_state / drop_training: as
+    gcn_encoder."""
+    return _Encoder.apply(_GIN, x_idx, graph, bns, DTYPES[precision],
+                          (drop_ratio, drop_state, drop_training), *params)
 
 
 def dropout_mask(drop_state, layer: int, p: float, N: int, D: int) -> torch.Tensor:

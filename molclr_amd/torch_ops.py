@@ -41,6 +41,7 @@ batch_norm_seg(z, gamma, beta, running   BatchNorm1d (+ ReLU) with one set of
   eps, relu)                             (ginet_molclr.py:105-111; a segment
                                          per encoder call, molclr.py:57,60)
 batch_norm_seg_bwd(...)                  its backward (dz, dgamma, dbeta)
+batch_norm_seg_bwd_frozen(...)           its eval-mode backward (running statistics)
 =======================================  =====================================
 
 GINEConv + BatchNorm (ginet_molclr.py:29-47,105-111) and GCNConv
@@ -686,6 +687,40 @@ def _(dy, z, gamma, beta, save_mean, save_invstd, seg_rows, relu):
     D = z.shape[1]
     return torch.empty_like(z), gamma.new_empty(D), gamma.new_empty(D)
 
+
+@custom_op("molclr::batch_norm_seg_bwd_frozen", mutates_args=(), device_types="cuda")
+def batch_norm_seg_bwd_frozen(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Tensor,
+                              beta: torch.Tensor, save_mean: torch.Tensor,
+                              save_invstd: torch.Tensor, seg_rows: list[int], relu: bool
+                              ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dz, dgamma, dbeta) of batch_norm_seg in eval mode: save_mean /
+    save_invstd are the running statistics its forward saved, dz = gamma *
+    invstd * dy behind the ReLU mask (molclr_batchnorm_seg_bwd_frozen)."""
+    _cuda(dy, z, gamma, beta, save_mean, save_invstd)
+    z = z.contiguous()
+    dy = dy.contiguous().to(z.dtype)
+    N, D = z.shape
+    rows, c_rows = _seg_rows_arg(seg_rows, N)
+    S = len(rows)
+    dt = _bn_dtype(z)
+    dz = torch.empty_like(z)
+    f32 = dict(dtype=torch.float32, device=z.device)
+    dg, dbt = torch.empty(D, **f32), torch.empty(D, **f32)
+    wsb = _lib.query("molclr_batchnorm_seg_workspace_bytes", S, c_rows, D)
+    ws = ops._ws(wsb, z.device)
+    _lib.call("molclr_batchnorm_seg_bwd_frozen", dy.data_ptr(), z.data_ptr(), gamma.data_ptr(),
+              beta.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(),
+              dg.data_ptr(), dbt.data_ptr(), S, c_rows, D, dt, int(bool(relu)), 0, ws.data_ptr(),
+              wsb, _stream(z))
+    return dz, dg, dbt
+
+
+@batch_norm_seg_bwd_frozen.register_fake
+def _(dy, z, gamma, beta, save_mean, save_invstd, seg_rows, relu):
+    D = z.shape[1]
+    return torch.empty_like(z), gamma.new_empty(D), gamma.new_empty(D)
+
+
 # ---------------------------------------------------------------------------
 # autograd
 # ---------------------------------------------------------------------------
@@ -810,12 +845,10 @@ def _bn_setup(ctx, inputs, output):
 
 
 def _bn_backward(ctx, dy, *_state):
-    if not ctx.training:
-        raise NotImplementedError("molclr::batch_norm_seg: no backward through eval mode (the "
-                                  "reference evaluates under torch.no_grad, molclr.py:162)")
     z, gamma, beta, mean, invstd = ctx.saved_tensors
-    dz, dg, db = torch.ops.molclr.batch_norm_seg_bwd(dy, z, gamma, beta, mean, invstd,
-                                                     ctx.seg_rows, ctx.relu)
+    bwd = torch.ops.molclr.batch_norm_seg_bwd if ctx.training \
+        else torch.ops.molclr.batch_norm_seg_bwd_frozen
+    dz, dg, db = bwd(dy, z, gamma, beta, mean, invstd, ctx.seg_rows, ctx.relu)
     return dz, dg, db, None, None, None, None, None, None, None, None
 
 
@@ -824,4 +857,4 @@ batch_norm_seg.register_autograd(_bn_backward, setup_context=_bn_setup)
 OPS = ("graph_build", "gine_aggregate", "gine_aggregate_bwd", "segment_pool", "segment_pool_bwd",
        "l2_normalize", "l2_normalize_bwd", "nt_xent", "nt_xent_bwd", "gcn_aggregate",
        "gcn_aggregate_bwd", "gcn_conv", "gcn_conv_bwd", "mlp", "mlp_bwd", "linear", "linear_bwd",
-       "batch_norm_seg", "batch_norm_seg_bwd")
+       "batch_norm_seg", "batch_norm_seg_bwd", "batch_norm_seg_bwd_frozen")

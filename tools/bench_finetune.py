@@ -26,7 +26,12 @@ step and evaluation pass against the captured ones, alternating round by round,
 with the launches per iteration of each (a replay's are the graph's kernel
 nodes plus the two staging launches).
 
-    python tools/bench_finetune.py [--rounds 9] [--iters 50] [--motif] [--out FILE]
+``--freeze-bn`` adds rows after the others: the eager step with batch
+statistics against the step with frozen BatchNorm (``model.freeze_bn``: running
+statistics, one backward pass over dy and z), GIN 5 x 300 and GCN 5 x 300,
+fp32, alternating round by round on one model, with the launches of each.
+
+    python tools/bench_finetune.py [--rounds 9] [--iters 50] [--motif] [--freeze-bn] [--out FILE]
 prints one JSON line per configuration.
 """
 import argparse
@@ -251,6 +256,42 @@ def run_motif(B, rounds, iters, dev, num_motifs=1000):
     return res
 
 
+def run_freeze(kind, B, rounds, iters, dev):
+    """The eager training step with batch statistics against the step with
+    frozen BatchNorm (model.freeze_bn) on ONE model, alternating round by round:
+    GIN 5 x 300 or GCN 5 x 300, fp32, drop_ratio 0; launches per step of each."""
+    from molclr_amd.gcn_finetune import GCN
+    torch.manual_seed(0)
+    if kind == "gcn":
+        model = GCN("classification", 5, 300, 512, 0.0, "mean").to(dev)
+    else:
+        model = GINet("classification", 5, 300, 512, 0.0, "mean", 2, "softplus").to(dev)
+    model.train()
+    opt = FusedAdam(model.parameters(), 1e-4, weight_decay=1e-6)
+    data = batches(B, 8, dev)
+
+    def step(i):
+        b, y = data[i % len(data)]
+        opt.zero_grad()
+        model.loss(b, y)[2].backward()
+        opt.step()
+
+    res = {"model": kind, "batch": B, "rounds": rounds, "iters": iters}
+    times = {0: [], 1: []}
+    for frozen in (0, 1):
+        model.freeze_bn = bool(frozen)
+        timed(step, 10)
+        res[f"launches_step_frozen{frozen}"] = launches(step)
+    for _ in range(rounds):
+        for frozen in (0, 1):
+            model.freeze_bn = bool(frozen)
+            times[frozen].append(timed(step, iters))
+    model.freeze_bn = False
+    for frozen, xs in times.items():
+        res[f"step_frozen{frozen}"] = summary(xs)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -258,6 +299,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--motif", action="store_true",
                     help="time the motif model, eager against captured, instead")
+    ap.add_argument("--freeze-bn", action="store_true",
+                    help="add rows: batch statistics against frozen BatchNorm (GIN and GCN)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     lines = []
@@ -268,6 +311,11 @@ def main():
         if a.motif:
             lines.append(json.dumps(run_motif(B, a.rounds, a.iters, dev)))
             print(lines[-1], flush=True)
+    if a.freeze_bn:
+        for kind in ("gin", "gcn"):
+            for B in (32, 256):
+                lines.append(json.dumps(run_freeze(kind, B, a.rounds, a.iters, dev)))
+                print(lines[-1], flush=True)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("\n".join(lines) + "\n")

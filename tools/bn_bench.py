@@ -1,5 +1,6 @@
 """BatchNorm backward at the c2 paired shape: molclr_batchnorm_seg_bwd against
-molclr_batchnorm_seg_bwd_max (dz's row maxima / max slot), per-call time."""
+molclr_batchnorm_seg_bwd_max (dz's row maxima / max slot), and the backward
+through frozen statistics (molclr_batchnorm_seg_bwd_frozen / _max), per-call time."""
 import ctypes
 import sys
 from pathlib import Path
@@ -57,6 +58,22 @@ def main():
         inv.data_ptr(), dz.data_ptr(), dg.data_ptr(), db.data_ptr(), 2, sr, D, 1, 1,
         parts.data_ptr(), slot.data_ptr(), ws.data_ptr(), ws_b, st))
     print(f"bn_bwd (3 kernels): plain {t0:.1f} us | row maxima {t1:.1f} us | + slot {t2:.1f} us")
+    # the backward through frozen statistics (one pass + the final): the same
+    # saved statistics serve as the frozen ones, only the time is of interest
+    f0 = timeit(lambda: lib.molclr_batchnorm_seg_bwd_frozen(
+        dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+        inv.data_ptr(), dz.data_ptr(), dg.data_ptr(), db.data_ptr(), 2, sr, D, 0, 1, 1,
+        ws.data_ptr(), ws_b, st))
+    f1 = timeit(lambda: lib.molclr_batchnorm_seg_bwd_frozen_max(
+        dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+        inv.data_ptr(), dz.data_ptr(), dg.data_ptr(), db.data_ptr(), 2, sr, D, 1, 1,
+        parts.data_ptr(), None, ws.data_ptr(), ws_b, st))
+    f2 = timeit(lambda: lib.molclr_batchnorm_seg_bwd_frozen_max(
+        dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+        inv.data_ptr(), dz.data_ptr(), dg.data_ptr(), db.data_ptr(), 2, sr, D, 1, 1,
+        parts.data_ptr(), slot.data_ptr(), ws.data_ptr(), ws_b, st))
+    print(f"bn_bwd frozen (2 kernels): plain {f0:.1f} us | row maxima {f1:.1f} us | "
+          f"+ slot {f2:.1f} us")
 
 
 if __name__ == "__main__":
