@@ -1398,6 +1398,81 @@ int molclr_eval_tail(const float* pred, const void* target, int64_t B, int64_t C
                      void* target_all, int64_t capacity, int64_t* cursor, double* loss_acc,
                      const int32_t* status_src, int32_t* status_acc, molclr_stream_t stream);
 
+/* ---- Device collate of labelled molecules (molclr_amd/task_store.py) ----------
+ * The fine-tuning counterpart of molclr_mask_views: MolTestDataset's molecules
+ * (dataset_test.py:114-169) resident in the molclr_mask_views store, featurised
+ * once, next to a target table -- int64 [G] class labels (target_is_float 0,
+ * target_cols 1) or fp32 [G, target_cols] -- and, for the motif model, the
+ * assignments as a CSR (motif_ptr int64 [G + 1], motif_ids int64).  mol_ids
+ * int64 [batch_size] on the device picks the batch, in any order, repeats
+ * allowed.  Every entry point runs on the given stream, allocates nothing and
+ * never synchronises; x / edge_attr buffers must be 16-byte aligned (their
+ * rows move as one 16-byte record).
+ *   molclr_collate_task (eager; a scan launch and a gather launch): the Batch
+ *     fields of Batch.from_data_list -- x_out [num_nodes, 2], edge_index_out
+ *     [2, num_edges] (local indices shifted by the molecule's first row),
+ *     edge_attr_out [num_edges, 2], batch_out [num_nodes], ptr_out
+ *     [batch_size + 1] -- molecule k's rows before molecule k + 1's, every
+ *     molecule's directed edges in store order, no bond dropped (num_edges =
+ *     2 Σ bonds); target_out int64 [batch_size] or fp32 [batch_size,
+ *     target_cols].  num_nodes / num_edges come from the host.  status [1] i32
+ *     (written, not ORed): bit 0 a molecule id out of range (it contributes no
+ *     rows, its target row is 0, nothing is read out of bounds), bit 1 the
+ *     host's num_nodes / num_edges are not the device's sums (nothing is stored
+ *     past them), bit 2 a stored edge index outside its molecule (clamped).
+ *   molclr_stage_task_ids (outside the captured region): the same gather into
+ *     the buffers molclr_stage_task fills -- x_all (rows [num_nodes,
+ *     num_nodes_cap) zeroed), the segment's edge_index (rows at stride
+ *     edge_cap), edge_attr and batch, counts = (num_nodes, num_edges),
+ *     target_dst.  batch_size must be dst->num_graphs.  Host sizes beyond the
+ *     capacities are refused before any launch with MOLCLR_ERR_ARG, by
+ *     molclr_stage_task's own plan and messages.  Device sums that disagree
+ *     with the host's set status bit 1 and counts = (0, 0); nothing is stored
+ *     past the capacities.  *status is written; the caller ORs it into its
+ *     sticky word.
+ *   molclr_motif_items (eager): mol_idx int64 [T + batch_size] and clique_idx
+ *     int64 [T] of the batch -- molecule 0's motif ids, molecule 1's, ..., each
+ *     with its position in the batch, then 0 .. batch_size - 1
+ *     (finetune.py:202-210).  T comes from the host.  status [1] (written): bit
+ *     0 a molecule id out of range (no items), bit 1 T is not the device's sum;
+ *     either makes the trailing batch_size rows of mol_idx -1.
+ *   molclr_stage_motif_ids (outside the captured region): those items, expanded
+ *     into the workspace, through molclr_stage_motif itself -- same buffers,
+ *     same stable sort, same status bits ORed into *status (T > T_cap:
+ *     MOLCLR_STATUS_ITEM_OVERFLOW; a refused id or a T that is not the device's
+ *     sum: MOLCLR_STATUS_ITEM_MOL, by the -1 rows above). */
+size_t molclr_collate_task_workspace_bytes(int64_t batch_size);
+int molclr_collate_task(const int64_t* store_x, const int64_t* store_atom_ptr,
+                        const int64_t* store_edge_index, const int64_t* store_edge_attr,
+                        const int64_t* store_bond_ptr, int64_t store_mols, int64_t store_edges,
+                        const int64_t* mol_ids, int64_t batch_size, const void* target_table,
+                        int64_t target_cols, int target_is_float, int64_t* x_out,
+                        int64_t* edge_index_out, int64_t* edge_attr_out, int64_t* batch_out,
+                        int64_t* ptr_out, void* target_out, int64_t num_nodes, int64_t num_edges,
+                        int32_t* status, void* workspace, size_t workspace_bytes,
+                        molclr_stream_t stream);
+/* workspace: molclr_collate_task_workspace_bytes(batch_size) */
+int molclr_stage_task_ids(const int64_t* store_x, const int64_t* store_atom_ptr,
+                          const int64_t* store_edge_index, const int64_t* store_edge_attr,
+                          const int64_t* store_bond_ptr, int64_t store_mols, int64_t store_edges,
+                          const int64_t* mol_ids, int64_t batch_size, const void* target_table,
+                          int64_t target_cols, int target_is_float, int64_t num_nodes,
+                          int64_t num_edges, const molclr_graph_staged_segment* dst,
+                          int64_t* x_all, int64_t num_nodes_cap, int64_t num_edges_cap,
+                          int64_t* counts, void* target_dst, int32_t* status, void* workspace,
+                          size_t workspace_bytes, molclr_stream_t stream);
+size_t molclr_motif_items_workspace_bytes(int64_t batch_size);
+int molclr_motif_items(const int64_t* motif_ptr, const int64_t* motif_ids, int64_t store_mols,
+                       const int64_t* mol_ids, int64_t batch_size, int64_t T, int64_t* mol_idx,
+                       int64_t* clique_idx, int32_t* status, void* workspace,
+                       size_t workspace_bytes, molclr_stream_t stream);
+size_t molclr_stage_motif_ids_workspace_bytes(int64_t batch_size, int64_t T_cap);
+int molclr_stage_motif_ids(const int64_t* motif_ptr, const int64_t* motif_ids, int64_t store_mols,
+                           const int64_t* mol_ids, int64_t batch_size, int64_t T, int64_t T_cap,
+                           int64_t* clique, int32_t* mol_ptr, int64_t* sorted_idx, int64_t* order,
+                           int32_t* status, void* workspace, size_t workspace_bytes,
+                           molclr_stream_t stream);
+
 /* ---- Benchmark instrumentation (no reference counterpart) -------------------
  * Opt-in kernel timer.  While a kind is enabled, its launches go through
  * hipExtLaunchKernelGGL with a start/stop event pair recorded by the dispatch

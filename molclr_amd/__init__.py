@@ -13,6 +13,7 @@ Every op runs on the HIP kernels of ``libmolclr_hip.so`` (C ABI:
 include/molclr.h), built in-tree by ``python -m molclr_amd.build``.
 """
 from .data import Batch, Data, DeviceGraph, collate_pairs, device_graph  # noqa: F401
+from .task_store import DeviceTaskLoader, DeviceTaskStore  # noqa: F401
 
 __version__ = "0.1.0"
 

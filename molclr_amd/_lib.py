@@ -222,6 +222,17 @@ SIGNATURES = {
     "molclr_stage_task": (c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, c_int, _P]),
     "molclr_task_step_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "molclr_eval_tail": (c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "molclr_collate_task_workspace_bytes": (c_size_t, [_I64]),
+    "molclr_collate_task": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, c_int, _P,
+                                    _P, _P, _P, _P, _P, _I64, _I64, _P, _P, c_size_t, _P]),
+    "molclr_stage_task_ids": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, c_int,
+                                      _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P, c_size_t,
+                                      _P]),
+    "molclr_motif_items_workspace_bytes": (c_size_t, [_I64]),
+    "molclr_motif_items": (c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, c_size_t, _P]),
+    "molclr_stage_motif_ids_workspace_bytes": (c_size_t, [_I64, _I64]),
+    "molclr_stage_motif_ids": (c_int, [_P, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P,
+                                       c_size_t, _P]),
     "molclr_ktimer_start": (c_int, [c_int]),
     "molclr_ktimer_read": (c_int, [c_int, _P, _P]),
     "molclr_ktimer_stop": (c_int, []),

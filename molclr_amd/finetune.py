@@ -20,7 +20,7 @@ built, loaded and given those rows as its motif table.  The motifs come from
 the optional key ``motifs``: ``builtin`` (molclr_amd.motifs' fragmenter, no
 RDKit, parity unpinned; the default) or the path of a JSON export of the
 reference's BRICS cliques.  Optional keys ``log_root``, ``ckpt_root``,
-``seed`` and ``hip_graph`` (default False): with ``hip_graph: True`` the
+``seed``, ``device_data`` and ``hip_graph`` (default False): with ``hip_graph: True`` the
 training step and the evaluation passes are replayed from HIP graphs
 (molclr_amd.finetune_step); a model those cannot take trains eagerly after
 one RuntimeWarning.  The motif model is taken with ``hip_graph_motif: True``
@@ -30,7 +30,11 @@ key it warns and trains eagerly.  ``model_type: gcn`` with ``fp16_precision:
 True`` trains in fp32 after a RuntimeWarning unless ``gcn_bf16: True`` (default
 False) is set too, which builds the GCN with ``precision='bf16'``.  ``freeze_bn:
 True`` (default False) keeps every BatchNorm of the encoder on its running
-statistics for the whole run (``model.freeze_bn``).  Invalid inputs (graph indices, atom features, class
+statistics for the whole run (``model.freeze_bn``).  ``device_data:
+True`` (default False) featurises the dataset once into HBM and collates every
+batch on the device (molclr_amd.task_store: DeviceTaskStore / DeviceTaskLoader);
+with ``hip_graph: True`` the captured steps gather each batch by its molecule
+ids straight into their buffers, the motif model's items included.  Invalid inputs (graph indices, atom features, class
 labels, motif indices) raise at the next log step (``check_inputs``), as in
 molclr_amd.molclr.
 """
@@ -155,6 +159,12 @@ class FineTune(object):
         self.hip_graph = bool(config.get('hip_graph', False))
         self.hip_graph_motif = bool(config.get('hip_graph_motif', False))
         self._captured = None
+        # device_data: True -- the dataset featurised once into HBM and every
+        # batch collated on the device (molclr_amd.task_store); off: the host
+        # DataLoader, exactly as before
+        self.device_data = bool(config.get('device_data', False))
+        self._store = None
+        self._collate_status = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def _get_device(self):
         if not torch.cuda.is_available() or self.config.get('gpu', 'cuda:0') == 'cpu':
@@ -278,6 +288,12 @@ class FineTune(object):
         """(data on the device, the motif model's (mol_idx, clique_idx) or
         None)."""
         motif = None
+        if self.device_data:  # a task_store batch: on the device already
+            if self.config['model_type'] == 'gin_motif':
+                motif = self._store.motif_items(data.mol_index,
+                                                getattr(data, "_molclr_host_ids", None))
+            torch.bitwise_or(self._collate_status, data.status, out=self._collate_status)
+            return data, motif
         if self.config['model_type'] == 'gin_motif':
             motif = self._motif_of(data)
         return data.to(self.device), motif
@@ -309,6 +325,15 @@ class FineTune(object):
                 st |= int(step.status.item())
             st |= ev._sticky
         raise_for_status(st)
+        if self.device_data:  # the device collates' own words
+            from .task_store import raise_for_collate_status
+            cst = int(self._collate_status.item())
+            if self._captured is not None:
+                step, ev = self._captured[2], self._captured[3]
+                if step is not None and step._made:
+                    cst |= int(step.collate_status.item())
+                cst |= ev._collate_sticky
+            raise_for_collate_status(cst)
 
     # -- hip_graph: True ----------------------------------------------------------
     def _captured_for(self, model, optimizers=None):
@@ -336,6 +361,10 @@ class FineTune(object):
 
     def train_step(self, model, optimizers, data):
         captured = self._captured_for(model, optimizers)
+        if captured is not None and self.device_data:
+            # data: (dev_ids, host_ids) of DeviceTaskLoader.ids(); the batch and
+            # the motif model's items are gathered into the graph's buffers
+            return captured[0].step_ids(self._store, *data).clone()
         if captured is not None:
             # the step's loss is its own buffer, overwritten by the next replay
             data, motif = self._to_device(data)
@@ -354,13 +383,24 @@ class FineTune(object):
         if self.config.get('seed') is not None:
             torch.manual_seed(int(self.config['seed']))
             np.random.seed(int(self.config['seed']))
-        smiles_data, train_loader, valid_loader, test_loader = self.dataset.get_data_loaders()
+        if self.device_data:
+            from . import task_store
+            smiles_data, self._store, train_loader, valid_loader, test_loader = \
+                task_store.device_loaders(self.dataset, self.device)
+        else:
+            smiles_data, train_loader, valid_loader, test_loader = self.dataset.get_data_loaders()
         if self.config['model_type'] == 'gin_motif':
             self.load_motifs(smiles_data)
+            if self.device_data:
+                self._store.set_motifs(self.assignments)
 
         self.normalizer = None
         if self.config['task_name'] in ['qm7', 'qm9']:
-            labels = torch.cat([d.y for d in train_loader])
+            if self.device_data:
+                train_ids = torch.from_numpy(train_loader.indices).to(self.device)
+                labels = self._store.y[train_ids]
+            else:
+                labels = torch.cat([d.y for d in train_loader])
             self.normalizer = Normalizer(labels.to(self.device))
 
         model = self.build_model()
@@ -376,7 +416,10 @@ class FineTune(object):
         self.epoch_train_loss = []
         for epoch_counter in range(self.config['epochs']):
             losses = []
-            for bn, data in enumerate(train_loader):
+            batches = train_loader
+            if self.device_data and self._captured_for(model, optimizers) is not None:
+                batches = train_loader.ids()  # the captured step gathers by ids
+            for bn, data in enumerate(batches):
                 loss = self.train_step(model, optimizers, data)
                 losses.append(loss.detach())
                 if n_iter % self.config['log_every_n_steps'] == 0:

@@ -91,6 +91,17 @@ def _is_motif(model) -> bool:
     return isinstance(model, MotifGINet)
 
 
+class _IdsBatch:
+    """A batch named by its molecule ids in a task_store.DeviceTaskStore:
+    what the captured steps take in place of a collated batch.  ``need``:
+    (nodes, edges, molecules[, motif items]) from the store's host counts."""
+
+    def __init__(self, store, dev_ids, host_ids):
+        self.store, self.dev_ids, self.host_ids = store, dev_ids, host_ids
+        self.sizes = store.sizes(host_ids)
+        self.need = self.sizes[:2] + (int(dev_ids.shape[0]),) + self.sizes[2:]
+
+
 class StagedTaskGraph(StagedPairGraph):
     """A one-segment StagedPairGraph with the batch's targets: ``target`` is
     int64 [B] (class labels) or fp32 [B, C], written by ``stage_task``."""
@@ -130,6 +141,38 @@ class StagedTaskGraph(StagedPairGraph):
                   _lib.stream_of(self.device))
         self._keep = [x, ei, ea, b, y]
 
+    def stage_task_ids(self, store, dev_ids, host_ids, sizes=None) -> None:
+        """The batch of the molecules ``dev_ids`` (int64, on the device) of a
+        task_store.DeviceTaskStore in -- what ``stage_task`` writes for the
+        collated batch, gathered from the store by ``molclr_stage_task_ids``
+        with no collated copy in between.  ``host_ids`` (or ``sizes``, from
+        ``store.sizes``) size the batch; ``ids_status`` gets the launch's
+        validity word (task_store.raise_for_collate_status)."""
+        B = self.graphs_per_segment[0]
+        if dev_ids.dim() != 1 or int(dev_ids.shape[0]) != B:
+            raise ValueError(f"StagedTaskGraph: {tuple(dev_ids.shape)} molecule ids, built for {B}")
+        if dev_ids.device.type != "cuda" or dev_ids.dtype != torch.long:
+            raise RuntimeError("StagedTaskGraph: the molecule ids must be int64 on the GPU")
+        if store.labels != self.labels or (not self.labels and store.cols != self.cols):
+            raise ValueError("StagedTaskGraph: the store's targets do not match the graph's "
+                             f"(labels {store.labels} / {self.labels}, columns {store.cols} / "
+                             f"{self.cols})")
+        n, e = (sizes if sizes is not None else store.sizes(host_ids))[:2]
+        if getattr(self, "ids_status", None) is None:
+            self.ids_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._ids_ws_bytes = _lib.query("molclr_collate_task_workspace_bytes", B)
+            self._ids_ws = torch.empty(self._ids_ws_bytes, dtype=torch.uint8, device=self.device)
+        dev_ids = dev_ids.contiguous()
+        _lib.call("molclr_stage_task_ids", store.x.data_ptr(), store.atom_ptr.data_ptr(),
+                  store.edge_index.data_ptr(), store.edge_attr.data_ptr(),
+                  store.bond_ptr.data_ptr(), store.num_molecules, int(store.edge_index.shape[1]),
+                  dev_ids.data_ptr(), B, store.y.data_ptr(), self.cols, int(not self.labels),
+                  int(n), int(e), ctypes.addressof(self._dst), self.x.data_ptr(), self.num_nodes,
+                  self.num_edges, self.counts.data_ptr(), self.target.data_ptr(),
+                  self.ids_status.data_ptr(), self._ids_ws.data_ptr(), self._ids_ws_bytes,
+                  _lib.stream_of(self.device))
+        self._keep = [dev_ids]
+
 
 class StagedMotifGraph(StagedTaskGraph):
     """A StagedTaskGraph that also holds the motif model's items in buffers of
@@ -168,6 +211,33 @@ class StagedMotifGraph(StagedTaskGraph):
                   self.sorted_idx.data_ptr(), self.order.data_ptr(), self.item_status.data_ptr(),
                   _lib.stream_of(self.device))
         self._keep_items = [mol_idx, clique_idx]
+
+    def stage_items_ids(self, store, dev_ids, host_ids, sizes=None) -> None:
+        """The items of the molecules ``dev_ids`` from the store's motif CSR
+        (``store.set_motifs``): exactly what ``stage_items`` writes for
+        ``motifs.motif_batch(ids, assignments)``, expanded on the device
+        (``molclr_stage_motif_ids``).  More items than ``item_cap`` are refused
+        on the device (``item_status``: STATUS_ITEM_OVERFLOW)."""
+        B = self.graphs_per_segment[0]
+        if store.motif_ptr is None:
+            raise RuntimeError("StagedMotifGraph: the store holds no motifs (set_motifs)")
+        if dev_ids.dim() != 1 or int(dev_ids.shape[0]) != B:
+            raise ValueError(f"StagedMotifGraph: {tuple(dev_ids.shape)} molecule ids, built for {B}")
+        if dev_ids.device.type != "cuda" or dev_ids.dtype != torch.long:
+            raise RuntimeError("StagedMotifGraph: the molecule ids must be int64 on the GPU")
+        T = (sizes if sizes is not None else store.sizes(host_ids))[2]
+        if getattr(self, "_items_ws", None) is None:
+            self._items_ws_bytes = _lib.query("molclr_stage_motif_ids_workspace_bytes", B,
+                                              self.item_cap)
+            self._items_ws = torch.empty(self._items_ws_bytes, dtype=torch.uint8,
+                                         device=self.device)
+        dev_ids = dev_ids.contiguous()
+        _lib.call("molclr_stage_motif_ids", store.motif_ptr.data_ptr(), store.motif_ids.data_ptr(),
+                  store.num_molecules, dev_ids.data_ptr(), B, int(T), self.item_cap,
+                  self.clique.data_ptr(), self.mol_ptr.data_ptr(), self.sorted_idx.data_ptr(),
+                  self.order.data_ptr(), self.item_status.data_ptr(), self._items_ws.data_ptr(),
+                  self._items_ws_bytes, _lib.stream_of(self.device))
+        self._keep_items = [dev_ids]
 
 
 class _CapturedTask:
@@ -220,7 +290,11 @@ class _CapturedTask:
         """(nodes, edges, molecules) of a batch, or of a size tuple; for the
         motif model a fourth term, the number of motif items (``items``: the
         count, ``(mol_idx, clique_idx)``, or the size tuple's fourth term)."""
-        if isinstance(data, tuple):
+        if isinstance(data, _IdsBatch):  # the size tuple of store.sizes, and the ids' count
+            if self.motif and len(data.need) != 4:
+                raise TypeError("the motif model's step needs the store's motifs (set_motifs)")
+            need = data.need
+        elif isinstance(data, tuple):
             need = tuple(int(v) for v in data)
         else:
             need = (int(data.x.shape[0]), int(data.edge_index.shape[1]), _num_graphs_of(data))
@@ -316,6 +390,12 @@ class _CapturedTask:
         return self.normalizer.norm(graph.target) if self.normalizer else graph.target
 
     def _stage(self, graph, data, items) -> None:
+        if isinstance(data, _IdsBatch):
+            graph.stage_task_ids(data.store, data.dev_ids, data.host_ids, data.sizes)
+            torch.bitwise_or(self.collate_status, graph.ids_status, out=self.collate_status)
+            if self.motif:
+                graph.stage_items_ids(data.store, data.dev_ids, data.host_ids, data.sizes)
+            return
         graph.stage_task(data)
         if self.motif:
             graph.stage_items(*items)
@@ -401,6 +481,8 @@ class _CapturedTask:
             for ent in self._graphs.values():
                 st |= int(ent.graph.item_status.item())
         raise_for_status(st)
+        from .task_store import raise_for_collate_status
+        raise_for_collate_status(int(self.collate_status.item()))  # step_ids' batches
 
     def close(self) -> None:
         """Release every captured graph (and its pool's memory) now."""
@@ -456,6 +538,8 @@ class CapturedFinetuneStep(_CapturedTask):
     def _alloc(self) -> None:
         self.loss = torch.zeros((), dtype=torch.float32, device=self.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # sticky OR of every stage_task_ids' validity word (step_ids)
+        self.collate_status = torch.zeros(1, dtype=torch.int32, device=self.device)
         # d loss / d loss from a tensor made before any capture: no fill
         # kernel in the graph for autograd's ones_like(loss)
         self._one = torch.ones((), dtype=torch.float32, device=self.device)
@@ -487,6 +571,18 @@ class CapturedFinetuneStep(_CapturedTask):
         ops.bump_param_generation()
         return self.loss
 
+    def step_ids(self, store, dev_ids, host_ids) -> torch.Tensor:
+        """``step`` of the batch of the molecules ``dev_ids`` (int64, on the
+        device; ``host_ids``: their host copy, which sizes the batch) of a
+        task_store.DeviceTaskStore: the batch is gathered from the store
+        straight into the graph's buffers, and the motif model's items from the
+        store's motif CSR."""
+        if not self.model.training:
+            raise RuntimeError("CapturedFinetuneStep: the model must be in training mode")
+        self._replay(_IdsBatch(store, dev_ids, host_ids))
+        ops.bump_param_generation()
+        return self.loss
+
     __call__ = step
 
 
@@ -510,7 +606,7 @@ class CapturedEval(_CapturedTask):
     kept, and rows past it are refused on the device (no store; the status
     bit STATUS_EVAL_OVERFLOW makes ``run`` raise)."""
 
-    _HEADER = 64  # bytes: cursor int64, loss sum fp64, status int32
+    _HEADER = 64  # bytes: cursor int64, loss sum fp64, status int32, collate status int32
 
     def __init__(self, model, criterion=None, normalizer=None, capacity: int | None = None,
                  node_quantum: int = 256, edge_quantum: int = 2048, max_graphs: int = 16,
@@ -521,6 +617,7 @@ class CapturedEval(_CapturedTask):
         self.fixed = capacity is not None
         self.capacity = int(capacity) if self.fixed else 0
         self._sticky = 0  # status bits of earlier passes (check())
+        self._collate_sticky = 0  # and of their device collates (a DeviceTaskLoader's)
 
     @contextlib.contextmanager
     def _mode(self):
@@ -552,6 +649,7 @@ class CapturedEval(_CapturedTask):
         self._layout = (self._HEADER, self._HEADER + pred_bytes)
         self.cursor, self.loss_acc, self.status, self.pred_all, self.target_all = \
             self._views(self._buf)
+        self.collate_status = self._buf[20:24].view(torch.int32)
 
     def _views(self, buf):
         p0, t0 = self._layout
@@ -585,7 +683,9 @@ class CapturedEval(_CapturedTask):
         return len(s) if s is not None and hasattr(s, "__len__") else None
 
     def run(self, loader, motif=None):
-        if self.motif and motif is None:
+        from .task_store import DeviceTaskLoader, raise_for_collate_status
+        by_ids = isinstance(loader, DeviceTaskLoader)  # staged by ids, items from the store
+        if self.motif and motif is None and not by_ids:
             raise TypeError("CapturedEval: the motif model's pass takes motif=callable, from a "
                             "host batch to its (mol_idx, clique_idx)")
         self._make_state()
@@ -598,13 +698,19 @@ class CapturedEval(_CapturedTask):
                 self._alloc_rows(rows)
         self._buf[:self._HEADER].zero_()
         with self._mode():
-            for data in loader:
-                items = motif(data) if self.motif else None
-                self._replay(data.to(self.device), items)
+            if by_ids:
+                for dev_ids, host_ids in loader.ids():
+                    self._replay(_IdsBatch(loader.store, dev_ids, host_ids))
+            else:
+                for data in loader:
+                    items = motif(data) if self.motif else None
+                    self._replay(data.to(self.device), items)
         host = self._buf.cpu()  # the pass's one synchronisation and one copy
         cursor, loss_acc, status, pred, tgt = self._views(host)
         self._sticky |= int(status.item())
+        self._collate_sticky |= int(host[20:24].view(torch.int32).item())
         raise_for_status(self._sticky)
+        raise_for_collate_status(self._collate_sticky)
         n = int(cursor.item())
         pred, tgt = pred[:n], tgt[:n]
         if self._denorm is not None:  # Normalizer.denorm, after the copy
@@ -613,7 +719,9 @@ class CapturedEval(_CapturedTask):
         return mean_loss, pred.numpy().copy(), tgt.reshape(-1).numpy().copy()
 
     def check(self) -> None:
+        from .task_store import raise_for_collate_status
         raise_for_status(self._sticky)
+        raise_for_collate_status(self._collate_sticky)
 
 
 __all__ = ["CapturedEval", "CapturedFinetuneStep", "StagedMotifGraph", "StagedTaskGraph",

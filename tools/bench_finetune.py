@@ -31,7 +31,13 @@ statistics against the step with frozen BatchNorm (``model.freeze_bn``: running
 statistics, one backward pass over dy and z), GIN 5 x 300 and GCN 5 x 300,
 fp32, alternating round by round on one model, with the launches of each.
 
-    python tools/bench_finetune.py [--rounds 9] [--iters 50] [--motif] [--freeze-bn] [--out FILE]
+``--loader`` adds rows after the others: the step's wall-clock with the loader
+in it (run_loader: a whole epoch of 64 batches of real SMILES per round) -- the
+trainer's host DataLoader (num_workers 0 and 8) against the device-resident
+task store (molclr_amd.task_store), each with the eager and the captured step.
+
+    python tools/bench_finetune.py [--rounds 9] [--iters 50] [--motif] [--freeze-bn] [--loader]
+                                   [--loader-rounds 5] [--out FILE]
 prints one JSON line per configuration.
 """
 import argparse
@@ -292,6 +298,98 @@ def run_freeze(kind, B, rounds, iters, dev):
     return res
 
 
+def run_loader(B, rounds, dev, nbatches=64):
+    """Wall-clock per training step INCLUDING the loader, a whole epoch of
+    ``nbatches`` batches per round over real SMILES (the lines of
+    tests/data/smiles_small.txt, repeated), GIN 5 x 300, drop_ratio 0:
+      host_w0 / host_w8        the trainer's DataLoader (num_workers 0 / 8:
+                               featurise, collate, copy) + the eager step
+      device_eager             DeviceTaskLoader (device collate) + the eager step
+      host_w0_captured / _w8_  the DataLoader + CapturedFinetuneStep.step
+      device_captured          DeviceTaskLoader.ids() + step_ids
+    The arms alternate round by round in one process; one untimed epoch of
+    each comes first (worker start-up, the first captures)."""
+    import tempfile
+
+    from molclr_amd.dataset_test import MolTestDatasetWrapper
+    from molclr_amd.task_store import device_loaders
+    root = Path(__file__).resolve().parent.parent
+    smiles = [l.strip() for l in (root / "tests" / "data" / "smiles_small.txt").read_text()
+              .splitlines() if l.strip()]
+    torch.manual_seed(0)
+    np.random.seed(0)
+    model = GINet("classification", 5, 300, 512, 0.0, "mean", 2, "softplus").to(dev)
+    model.train()
+    opt = FusedAdam(model.parameters(), 1e-4, weight_decay=1e-6)
+    cstep = CapturedFinetuneStep(model, opt, "cross_entropy")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = Path(tmp) / "data.csv"
+        with open(path, "w") as f:
+            f.write("smiles,label\nC,0\n")  # the first data row is skipped
+            for i in range(nbatches * B):
+                f.write(f"{smiles[i % len(smiles)]},{i % 2}\n")
+
+        def wrapper(workers):
+            return MolTestDatasetWrapper(B, workers, 0.0, 0.0, "classification", str(path),
+                                         "label", "random")
+
+        t0 = time.perf_counter()
+        _, store, dev_loader, _, _ = device_loaders(wrapper(0), dev)
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - t0
+        host = {w: wrapper(w).get_data_loaders()[1] for w in (0, 8)}
+        assert len(dev_loader) == nbatches and all(len(l) == nbatches for l in host.values())
+
+        def eager(data):
+            opt.zero_grad()
+            model.loss(data, data.y.flatten())[2].backward()
+            opt.step()
+
+        def host_epoch(workers, captured):
+            for data in host[workers]:
+                data = data.to(dev)  # FineTune._to_device
+                cstep.step(data) if captured else eager(data)
+
+        def device_epoch(captured):
+            if captured:
+                for ids_d, ids_h in dev_loader.ids():
+                    cstep.step_ids(store, ids_d, ids_h)
+            else:
+                for data in dev_loader:
+                    eager(data)
+
+        arms = {"host_w0": lambda: host_epoch(0, False), "host_w8": lambda: host_epoch(8, False),
+                "device_eager": lambda: device_epoch(False),
+                "host_w0_captured": lambda: host_epoch(0, True),
+                "host_w8_captured": lambda: host_epoch(8, True),
+                "device_captured": lambda: device_epoch(True)}
+        res = {"loader": True, "batch": B, "batches_per_epoch": nbatches, "rounds": rounds,
+               "molecules": store.num_molecules, "store_build_s": round(build_s, 3)}
+        for fn in arms.values():
+            fn()
+        torch.cuda.synchronize()
+        captures_before = cstep.captures
+        times = {name: [] for name in arms}
+        for _ in range(rounds):
+            for name, fn in arms.items():
+                times[name].append(timed(lambda i: fn(), 1) / nbatches)
+        res["captures_in_timed_region"] = cstep.captures - captures_before
+        res["buckets_step"] = cstep.buckets
+        cstep.check()
+    for name, xs in times.items():
+        res[name] = summary(xs)
+
+    def below(a, *bs):  # a's slowest round under the fastest round of the better of bs
+        best = min(bs, key=lambda b: res[b]["median_us"])
+        return res[a]["max_us"] < res[best]["min_us"]
+
+    res["device_eager_below_host"] = below("device_eager", "host_w0", "host_w8")
+    res["device_captured_below_host_captured"] = below("device_captured", "host_w0_captured",
+                                                       "host_w8_captured")
+    cstep.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -301,6 +399,10 @@ def main():
                     help="time the motif model, eager against captured, instead")
     ap.add_argument("--freeze-bn", action="store_true",
                     help="add rows: batch statistics against frozen BatchNorm (GIN and GCN)")
+    ap.add_argument("--loader", action="store_true",
+                    help="add rows: wall-clock per step with the loader in it, the host "
+                         "DataLoader against the device-resident task store")
+    ap.add_argument("--loader-rounds", type=int, default=5)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     lines = []
@@ -316,6 +418,10 @@ def main():
             for B in (32, 256):
                 lines.append(json.dumps(run_freeze(kind, B, a.rounds, a.iters, dev)))
                 print(lines[-1], flush=True)
+    if a.loader:
+        for B in (32, 256):
+            lines.append(json.dumps(run_loader(B, a.loader_rounds, dev)))
+            print(lines[-1], flush=True)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("\n".join(lines) + "\n")
