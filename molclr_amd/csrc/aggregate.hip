@@ -1137,10 +1137,7 @@ int molclr::edge_tables_combine_zero(int layers, const float* const* E1s, const 
 }
 
 static bool agg_nt() {
-  static const bool on = [] {
-    const char* e = getenv("MOLCLR_AGG_NT");
-    return e != nullptr && e[0] == '1';
-  }();
+  static const bool on = molclr::env_is("MOLCLR_AGG_NT", '1');
   return on;
 }
 
@@ -1202,10 +1199,7 @@ MOLCLR_API size_t molclr_gine_aggregate_bwd_workspace_bytes(int64_t N, int64_t D
 // dx and the edge-table partials in one pass (default) or by the two kernels
 // (MOLCLR_AGG_BWD_FUSED=0, an A/B switch)
 static bool agg_bwd_fused() {
-  static const bool on = [] {
-    const char* e = getenv("MOLCLR_AGG_BWD_FUSED");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = !molclr::env_is("MOLCLR_AGG_BWD_FUSED", '0');
   return on;
 }
 

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 
 #include "../../include/molclr.h"
 #include "dropout.h"
@@ -45,6 +46,18 @@ inline int cu_count() {
     cached[dev] = n;
   }
   return cached[dev];
+}
+
+// Environment knobs: whether `name` is set and begins with `c`, and its
+// atoi value (dflt when unset).  A knob is read once per process: callers
+// keep the result in a function-local `static const`.
+inline bool env_is(const char* name, char c) {
+  const char* e = getenv(name);
+  return e != nullptr && e[0] == c;
+}
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

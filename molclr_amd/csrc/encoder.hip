@@ -32,10 +32,7 @@ namespace {
 // the next layer's aggregation applies the BatchNorm (default) or reads a
 // stored h_l (MOLCLR_AGG_BN=0)
 bool agg_bn() {
-  static const bool on = [] {
-    const char* e = getenv("MOLCLR_AGG_BN");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = !molclr::env_is("MOLCLR_AGG_BN", '0');
   return on;
 }
 

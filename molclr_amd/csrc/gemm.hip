@@ -1643,12 +1643,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
 // ---------------------------------------------------------------------------
 constexpr int kBN = 128;  // columns per tile (TN = 4)
 constexpr int kTN = 4;
-constexpr int kFullImg = 2 * kBN * XK;  // fp16 elements of one full K step (both planes)
-constexpr int kHalfImg = 2 * kBN * 16;  // ... of a last step holding k0 .. k0+15 only
+// fp16 elements of a bn-column tile's image (both planes): of one full K step,
+// and of all S steps, the last holding k0 .. k0+15 only when `half`
+constexpr int bs_step_img(int bn) { return 2 * bn * XK; }
+constexpr int bs_img(int bn, int s, bool half) {
+  return (half ? s - 1 : s) * bs_step_img(bn) + (half ? 2 * bn * 16 : 0);
+}
 
 // offset (fp16 units) of chunk c (0 or 1) of row `row` in a half-step plane:
 // 32 B per row, the two chunks swapped on alternate row quads
 __device__ __forceinline__ int hoff(int row, int c) { return row * 16 + ((c ^ ((row >> 2) & 1)) << 3); }
+
+// the ReLU-mask words of row `arow` for the tile's TN 32-column groups from
+// column n0 (a group past N reads word 0 and is not used)
+template <int TN>
+__device__ __forceinline__ void bs_mask_words(uint32_t (&mws)[TN], const uint32_t* bits_in,
+                                              int64_t bits_ld, int64_t n0, int64_t N,
+                                              int64_t arow) {
+#pragma unroll
+  for (int b = 0; b < TN; ++b) {
+    int64_t nb = n0 + 32 * b;
+    nb = nb < N ? nb : 0;
+    mws[b] = bits_in[(nb >> 5) * bits_ld + arow];
+  }
+}
 
 // Pipelined across slabs:  A wave's next slab --
 // its row maxima, ReLU-mask words and first two A steps -- is issued during
@@ -1668,8 +1686,8 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     int ntn, int groups) {
   static_assert(S % 2 == 0 && S >= 4, "two A register sets, steps in pairs");
   constexpr int NFULL = HALF ? S - 1 : S;
-  constexpr int IMG = NFULL * kFullImg + (HALF ? kHalfImg : 0);
-  __shared__ __attribute__((aligned(16))) uint16_t img[IMG];
+  constexpr int FULL = bs_step_img(kBN);
+  __shared__ __attribute__((aligned(16))) uint16_t img[bs_img(kBN, S, HALF)];
   __shared__ __attribute__((aligned(16))) float bsh[kBN];
 
   const int tid = threadIdx.x;
@@ -1693,7 +1711,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
       int64_t gr = n0 + row;
       gr = gr < npad ? gr : npad - 1;
       const uint32_t voff = (uint32_t)(((pl * npad + gr) * kp + 32 * st + 8 * (c ^ ((row >> 2) & 3))) * 2);
-      buf_lds16(brsrc, img + st * kFullImg + pl * kBN * XK + r0 * XK, voff, 0);
+      buf_lds16(brsrc, img + st * FULL + pl * kBN * XK + r0 * XK, voff, 0);
     }
     if constexpr (HALF) {
       constexpr int CHH = 2 * (kBN / 32);
@@ -1704,12 +1722,12 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
         gr = gr < npad ? gr : npad - 1;
         const uint32_t voff =
             (uint32_t)(((pl * npad + gr) * kp + 32 * (S - 1) + 8 * (c ^ ((row >> 2) & 1))) * 2);
-        buf_lds16(brsrc, img + NFULL * kFullImg + pl * kBN * 16 + r0 * 16, voff, 0);
+        buf_lds16(brsrc, img + NFULL * FULL + pl * kBN * 16 + r0 * 16, voff, 0);
       }
     }
-    if constexpr (HAS_BIAS) {
-      if (tid < kBN) bsh[tid] = n0 + tid < N ? bias[n0 + tid] : 0.f;
-    }
+  }
+  if constexpr (HAS_BIAS) {
+    if (tid < kBN) bsh[tid] = n0 + tid < N ? bias[n0 + tid] : 0.f;
   }
   const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(A, M * lda * 4);
   float cm = 0.f, ain = 0.f;
@@ -1741,14 +1759,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
         for (int p = 0; p < 8; ++p) rw[p] = amax[(int64_t)(p < arow_parts ? p : 0) * M + arow];
       }
     }
-    if constexpr (EPI == MOLCLR_EPI_RELU_MASK) {
-#pragma unroll
-      for (int b = 0; b < kTN; ++b) {
-        int64_t nb = n0 + 32 * b;
-        nb = nb < N ? nb : 0;
-        mws[b] = bits_in[(nb >> 5) * bits_ld + arow];
-      }
-    }
+    if constexpr (EPI == MOLCLR_EPI_RELU_MASK) bs_mask_words(mws, bits_in, bits_ld, n0, N, arow);
   };
   auto row_shift = [&]() -> int {
     if constexpr (H3 == 1) return h3_shift(amax);
@@ -1807,7 +1818,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     }
   };
   auto compute_half = [&]() {
-    const uint16_t* base = img + NFULL * kFullImg;
+    const uint16_t* base = img + NFULL * FULL;
     const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 2 * kTN; ++k) {
@@ -1863,11 +1874,11 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
       if (r > 0) vm_wait<4>();
       split(ar0, r, sha);
       load_a(r + 2, ar0);
-      compute(img + r * kFullImg);
+      compute(img + r * FULL);
       if (r > 0) vm_wait<4>();
       split(ar1, r + 1, sha);
       load_a(r + 3, ar1);
-      compute(img + (r + 1) * kFullImg);
+      compute(img + (r + 1) * FULL);
     }
     // steps S-2, S-1: the next slab's state and first two A steps go out
     const int sha_cur = sha;
@@ -1881,13 +1892,13 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
         meta_issue(next);
         load_a(0, ar0);
       }
-      compute(img + (S - 2) * kFullImg);
+      compute(img + (S - 2) * FULL);
       if (more) vm_wait<8>();  // A(S-1) landed; the next slab's loads may be in flight
       else vm_wait<0>();
       split(a9, S - 1, sha_cur);
       if (more) load_a(1, ar1);
       if (HALF) compute_half();
-      else compute(img + (S - 1) * kFullImg);
+      else compute(img + (S - 1) * FULL);
     }
     // the next slab's loads landed before any store is issued
     vm_wait<0>();
@@ -1992,13 +2003,12 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     uint32_t* __restrict__ bits_out, const uint32_t* __restrict__ bits_in, int64_t bits_ld,
     int ntn, int groups) {
   static_assert(S >= 4 && (S % 2 == 0 || !HALF), "steps in pairs, or an odd count of full steps");
-  constexpr int kBN = BNT, kTN = BNT / 32;  // this tile (k_gemm_bs's constants shadowed)
-  constexpr int kFullImg = 2 * kBN * XK, kHalfImg = 2 * kBN * 16;
   constexpr int NFULL = HALF ? S - 1 : S;
-  constexpr int IMG = NFULL * kFullImg + (HALF ? kHalfImg : 0);
-  constexpr int NB = kBN / 16;  // 16-column blocks of the tile
-  __shared__ __attribute__((aligned(16))) uint16_t img[IMG];
-  __shared__ __attribute__((aligned(16))) float bsh[kBN];
+  constexpr int FULL = bs_step_img(BNT);
+  constexpr int NB = BNT / 16;  // 16-column blocks of the tile
+  constexpr int NG = BNT / 32;  // 32-column groups (a ReLU-bit word each)
+  __shared__ __attribute__((aligned(16))) uint16_t img[bs_img(BNT, S, HALF)];
+  __shared__ __attribute__((aligned(16))) float bsh[BNT];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -2006,39 +2016,39 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
   const int r16 = lane & 15, q4 = lane >> 4;
   const int L = xcd_remap(blockIdx.x, gridDim.x);
   const int tile = L % ntn, grp = L / ntn;
-  const int64_t n0 = (int64_t)tile * kBN;
+  const int64_t n0 = (int64_t)tile * BNT;
   const int64_t slabs = (M + 15) / 16;
   const int64_t s_beg = slabs * grp / groups, s_end = slabs * (grp + 1) / groups;
   constexpr bool HAS_BIAS = EPI == MOLCLR_EPI_BIAS || EPI == MOLCLR_EPI_BIAS_RELU;
 
-  // the B image: as k_gemm_bs
   const __amdgpu_buffer_rsrc_t brsrc = make_rsrc(Bp, (int64_t)2 * npad * kp * 2);
+  // the B image: as k_gemm_bs, with bsn's swizzle
   {
-    constexpr int CHF = NFULL * 2 * (kBN / 16);
+    constexpr int CHF = NFULL * 2 * (BNT / 16);
     for (int q = w; q < CHF; q += W) {
-      const int st = q / (2 * (kBN / 16)), rem = q % (2 * (kBN / 16));
-      const int pl = rem / (kBN / 16), r0 = (rem % (kBN / 16)) * 16;
+      const int st = q / (2 * (BNT / 16)), rem = q % (2 * (BNT / 16));
+      const int pl = rem / (BNT / 16), r0 = (rem % (BNT / 16)) * 16;
       const int row = r0 + (lane >> 2), c = lane & 3;
       int64_t gr = n0 + row;
       gr = gr < npad ? gr : npad - 1;
       const uint32_t voff = (uint32_t)(((pl * npad + gr) * kp + 32 * st + 8 * (c ^ bsn_swz(row))) * 2);
-      buf_lds16(brsrc, img + st * kFullImg + pl * kBN * XK + r0 * XK, voff, 0);
+      buf_lds16(brsrc, img + st * FULL + pl * BNT * XK + r0 * XK, voff, 0);
     }
     if constexpr (HALF) {
-      constexpr int CHH = 2 * (kBN / 32);
+      constexpr int CHH = 2 * (BNT / 32);
       for (int q = w; q < CHH; q += W) {
-        const int pl = q / (kBN / 32), r0 = (q % (kBN / 32)) * 32;
+        const int pl = q / (BNT / 32), r0 = (q % (BNT / 32)) * 32;
         const int row = r0 + (lane >> 1), c = lane & 1;
         int64_t gr = n0 + row;
         gr = gr < npad ? gr : npad - 1;
         const uint32_t voff =
             (uint32_t)(((pl * npad + gr) * kp + 32 * (S - 1) + 8 * (c ^ ((row >> 2) & 1))) * 2);
-        buf_lds16(brsrc, img + NFULL * kFullImg + pl * kBN * 16 + r0 * 16, voff, 0);
+        buf_lds16(brsrc, img + NFULL * FULL + pl * BNT * 16 + r0 * 16, voff, 0);
       }
     }
-    if constexpr (HAS_BIAS) {
-      if (tid < kBN) bsh[tid] = n0 + tid < N ? bias[n0 + tid] : 0.f;
-    }
+  }
+  if constexpr (HAS_BIAS) {
+    if (tid < BNT) bsh[tid] = n0 + tid < N ? bias[n0 + tid] : 0.f;
   }
   const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(A, M * lda * 4);
   float cm = 0.f, ain = 0.f;
@@ -2046,7 +2056,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
   int64_t arow = 0;
   uint32_t avoff = 0;
   float rw[8];
-  uint32_t mws[kTN];
+  uint32_t mws[NG];
   auto meta_issue = [&](int64_t slab) {
     arow = slab * 16 + r16;
     arow = arow < M ? arow : M - 1;
@@ -2068,14 +2078,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
         for (int p = 0; p < 8; ++p) rw[p] = amax[(int64_t)(p < arow_parts ? p : 0) * M + arow];
       }
     }
-    if constexpr (EPI == MOLCLR_EPI_RELU_MASK) {
-#pragma unroll
-      for (int g = 0; g < kTN; ++g) {
-        int64_t nb = n0 + 32 * g;
-        nb = nb < N ? nb : 0;
-        mws[g] = bits_in[(nb >> 5) * bits_ld + arow];
-      }
-    }
+    if constexpr (EPI == MOLCLR_EPI_RELU_MASK) bs_mask_words(mws, bits_in, bits_ld, n0, N, arow);
   };
   auto row_shift = [&]() -> int {
     if constexpr (H3 == 1) return h3_shift(amax);
@@ -2108,7 +2111,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     auto rd = [&](int b, u32x4(&f)[2]) {
       const int row = 16 * b + r16;
       f[0] = *reinterpret_cast<const u32x4*>(base + bsn_off(row, q4));
-      f[1] = *reinterpret_cast<const u32x4*>(base + kBN * XK + bsn_off(row, q4));
+      f[1] = *reinterpret_cast<const u32x4*>(base + BNT * XK + bsn_off(row, q4));
     };
     u32x4 q[2][2];
     rd(0, q[0]);
@@ -2131,14 +2134,14 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
   };
   // the last step holds k0 .. k0+15 only: lanes q4 >= 2 (k0+16 ..) take zeros
   auto compute_half = [&]() {
-    const uint16_t* base = img + NFULL * kFullImg;
+    const uint16_t* base = img + NFULL * FULL;
     const u32x4 z = {0u, 0u, 0u, 0u};
     const int c = q4 & 1;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       const int row = 16 * b + r16;
       const u32x4 h = *reinterpret_cast<const u32x4*>(base + hoff(row, c));
-      const u32x4 l = *reinterpret_cast<const u32x4*>(base + kBN * 16 + hoff(row, c));
+      const u32x4 l = *reinterpret_cast<const u32x4*>(base + BNT * 16 + hoff(row, c));
       acc[b] = mfma16_h3_t(__builtin_bit_cast(f16x8, frh), __builtin_bit_cast(f16x8, frl),
                            __builtin_bit_cast(f16x8, q4 >= 2 ? z : h),
                            __builtin_bit_cast(f16x8, q4 >= 2 ? z : l), acc[b]);
@@ -2177,20 +2180,20 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[b][r] = 0.f;
-    uint32_t mcur[kTN];
+    uint32_t mcur[NG];
 #pragma unroll
-    for (int g = 0; g < kTN; ++g) mcur[g] = mws[g];
+    for (int g = 0; g < NG; ++g) mcur[g] = mws[g];
     constexpr int SP = S % 2 ? S - 3 : S - 2;  // steps taken in pairs
 #pragma unroll 1
     for (int r = 0; r < SP; r += 2) {
       if (r > 0) vm_wait<2>();
       split(ar0, r, sha);
       load_a(r + 2, ar0);
-      compute(img + r * kFullImg);
+      compute(img + r * FULL);
       if (r > 0) vm_wait<2>();
       split(ar1, r + 1, sha);
       load_a(r + 3, ar1);
-      compute(img + (r + 1) * kFullImg);
+      compute(img + (r + 1) * FULL);
     }
     const int sha_cur = sha;
     const int64_t mw_cur = mw;
@@ -2200,19 +2203,19 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
       vm_wait<2>();
       split(ar0, S - 3, sha_cur);
       load_a(S - 1, ar0);
-      compute(img + (S - 3) * kFullImg);
+      compute(img + (S - 3) * FULL);
       vm_wait<2>();
       split(ar1, S - 2, sha_cur);
       if (more) {
         meta_issue(next);
         load_a(0, ar1);
       }
-      compute(img + (S - 2) * kFullImg);
+      compute(img + (S - 2) * FULL);
       if (more) vm_wait<4>();
       else vm_wait<0>();
       split(ar0, S - 1, sha_cur);
       if (more) load_a(1, ar0);  // split consumed ar0
-      compute(img + (S - 1) * kFullImg);
+      compute(img + (S - 1) * FULL);
       if (more) {
         const float4 x0 = ar0[0], x1 = ar0[1];
         ar0[0] = ar1[0];
@@ -2227,13 +2230,13 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
         meta_issue(next);
         load_a(0, ar0);
       }
-      compute(img + (S - 2) * kFullImg);
+      compute(img + (S - 2) * FULL);
       if (more) vm_wait<4>();
       else vm_wait<0>();
       split(ar1, S - 1, sha_cur);
       if (more) load_a(1, ar1);
       if (HALF) compute_half();
-      else compute(img + (S - 1) * kFullImg);
+      else compute(img + (S - 1) * FULL);
     }
     vm_wait<0>();  // the next slab's loads landed before any store is issued
     if (more) {
@@ -2247,7 +2250,7 @@ __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(W / 4)))
     float rmax = 0.f;
     int rmaxi = 0;
 #pragma unroll
-    for (int g = 0; g < kTN; ++g) {  // 32-column groups (a ReLU-bit word each)
+    for (int g = 0; g < NG; ++g) {  // 32-column groups (a ReLU-bit word each)
       const int64_t ng = n0 + 32 * g;
       if (ng >= N) break;
       uint32_t pos = 0;
@@ -3053,37 +3056,47 @@ int64_t q6_blocks(int64_t M, int64_t N) {
 // count for products of at least 8 K steps (a diagnostic: the K-chain length
 // of the fp32 sums, tools/order_spread.py).
 int q6_groups(int64_t M, int64_t N, int64_t K) {
-  static const int forced = [] {
-    const char* e = getenv("MOLCLR_Q6_GROUPS");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = env_int("MOLCLR_Q6_GROUPS", 0);
   if ((K + BK - 1) / BK < 8) return 1;
   if (forced == 1 || forced == 2) return forced;
   return q6_blocks(M, N) < 384 ? 2 : 1;
 }
 
+// The launch of a pre-split-B kernel of the q6 family (k_gemm_q6, k_gemm_pp,
+// k_gemm_bs, k_gemm_bsn: one argument list); tail: the bs kernels' ntn, groups
+template <typename Kern, typename... Tail>
+void launch_h3(Kern kern, dim3 grid, dim3 block, const Args& a, int64_t npad, hipStream_t s,
+               Tail... tail) {
+  molclr::launch_timed(molclr::kTimeGemm, kern, grid, block, 0, s, a.A, a.Bp, a.C, a.M, a.N, a.K,
+                       a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate, a.amax,
+                       a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out, a.bits_in,
+                       a.bits_ld, tail...);
+}
+// fn(std::integral_constant<int, epi>{}) for the runtime epilogue; -1: unknown
+template <typename F>
+int with_epi(int epi, F&& fn) {
+  switch (epi) {
+    case MOLCLR_EPI_NONE: fn(std::integral_constant<int, MOLCLR_EPI_NONE>{}); return 0;
+    case MOLCLR_EPI_BIAS: fn(std::integral_constant<int, MOLCLR_EPI_BIAS>{}); return 0;
+    case MOLCLR_EPI_BIAS_RELU: fn(std::integral_constant<int, MOLCLR_EPI_BIAS_RELU>{}); return 0;
+    case MOLCLR_EPI_RELU_MASK: fn(std::integral_constant<int, MOLCLR_EPI_RELU_MASK>{}); return 0;
+    default: return -1;
+  }
+}
+
 template <int TN, int EPI, int KG, bool MASK, int H3>
 void launch_q6_t(const Args& a, int64_t npad, hipStream_t s) {
-  molclr::launch_timed(molclr::kTimeGemm, (k_gemm_q6<TN, EPI, KG, MASK, H3>),
-                       dim3((unsigned)q6_blocks(a.M, a.N)), dim3(KG * 64 * kQ6Waves), 0, s, a.A,
-                       a.Bp, a.C, a.M, a.N, a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux,
-                       a.accumulate, a.amax, a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts,
-                       a.bits_out, a.bits_in, a.bits_ld);
+  launch_h3(k_gemm_q6<TN, EPI, KG, MASK, H3>, dim3((unsigned)q6_blocks(a.M, a.N)),
+            dim3(KG * 64 * kQ6Waves), a, npad, s);
 }
 // the ping-pong form: one K group, five-block tiles, byte ranges within the
 // buffer descriptors' 31-bit records (MOLCLR_Q6_PP=0 keeps k_gemm_q6)
 bool q6_pp_ok(const Args& a, int64_t npad, int tn, int kg, int h3) {
-  static const int off = [] {
-    const char* e = getenv("MOLCLR_Q6_PP");
-    return e && e[0] == '0';
-  }();
+  static const bool off = env_is("MOLCLR_Q6_PP", '0');
   const int64_t kp = (a.K + BK - 1) / BK * BK;
   // narrow h3 products (<= 2 column tiles: 30 MFMAs per phase over 19 steps
   // at K = 600) measured slower in the step (dagg 53.0 -> 57.9 us): q6
-  static const bool narrow = [] {
-    const char* e = getenv("MOLCLR_PP_NARROW");
-    return e != nullptr && e[0] == '1';
-  }();
+  static const bool narrow = env_is("MOLCLR_PP_NARROW", '1');
   if (h3 && a.N <= 320 && !narrow) return false;
   return !off && kg == 1 && tn == 5 && a.M * a.lda * 4 < (1ll << 31) &&
          (int64_t)(h3 ? 2 : 3) * npad * kp * 2 < (1ll << 31) && a.lda % 4 == 0;
@@ -3091,10 +3104,7 @@ bool q6_pp_ok(const Args& a, int64_t npad, int tn, int kg, int h3) {
 // the h3 products take k_gemm_pp's swapped register epilogue; MOLCLR_PP_SWAP=0
 // keeps the LDS-transpose epilogue
 bool pp_swap() {
-  static const bool on = [] {
-    const char* e = getenv("MOLCLR_PP_SWAP");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = !env_is("MOLCLR_PP_SWAP", '0');
   return on;
 }
 template <int TN, int EPI, int H3>
@@ -3102,10 +3112,7 @@ void launch_pp(const Args& a, int64_t npad, hipStream_t s) {
   const int64_t bn = 32 * TN;
   const int64_t blocks = ((a.M + kPPRows - 1) / kPPRows) * ((a.N + bn - 1) / bn);
   auto kern = (H3 != 0 && pp_swap()) ? k_gemm_pp<TN, EPI, H3, H3 != 0> : k_gemm_pp<TN, EPI, H3, false>;
-  molclr::launch_timed(molclr::kTimeGemm, kern, dim3((unsigned)blocks),
-                       dim3(512), 0, s, a.A, a.Bp, a.C, a.M, a.N, a.K, a.lda, a.ldb, npad, a.ldc,
-                       a.bias, a.aux, a.ldaux, a.accumulate, a.amax, a.bmax, a.cmax, a.crow,
-                       a.amax_out, a.arow_parts, a.bits_out, a.bits_in, a.bits_ld);
+  launch_h3(kern, dim3((unsigned)blocks), dim3(512), a, npad, s);
 }
 template <int TN, int EPI, int H3>
 void launch_q6(const Args& a, int64_t npad, hipStream_t s) {
@@ -3129,25 +3136,14 @@ void launch_q6(const Args& a, int64_t npad, hipStream_t s) {
   }
 }
 
-template <int TN, int H3>
-int dispatch_q6(int epi, const Args& a, int64_t npad, hipStream_t s) {
-  switch (epi) {
-    case MOLCLR_EPI_NONE: launch_q6<TN, MOLCLR_EPI_NONE, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS: launch_q6<TN, MOLCLR_EPI_BIAS, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS_RELU: launch_q6<TN, MOLCLR_EPI_BIAS_RELU, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_RELU_MASK: launch_q6<TN, MOLCLR_EPI_RELU_MASK, H3>(a, npad, s); return 0;
-    default: return -1;
-  }
-}
-
 // a.ldb = kp (the planes' row pitch), a.Bp = the planes; h3 1 / 2: fp16
 // two-part planes, a.amax (a slot / row maxima) and a.bmax set
-template <int H3>
-int dispatch_q6_tn(int epi, const Args& a, int64_t npad, hipStream_t s) {
+template <int EPI, int H3>
+void launch_q6_tn(const Args& a, int64_t npad, hipStream_t s) {
   const int tn = wide_tn(a.N);
-  return tn == 5 ? dispatch_q6<5, H3>(epi, a, npad, s)
-         : tn == 4 ? dispatch_q6<4, H3>(epi, a, npad, s)
-                   : dispatch_q6<2, H3>(epi, a, npad, s);
+  if (tn == 5) launch_q6<5, EPI, H3>(a, npad, s);
+  else if (tn == 4) launch_q6<4, EPI, H3>(a, npad, s);
+  else launch_q6<2, EPI, H3>(a, npad, s);
 }
 // The h3 products k_gemm_bs takes: K in (288, 304] (its LDS image), wide
 // (> 320 columns), float4-aligned C, ReLU masks as bits, row maxima as a slot,
@@ -3174,20 +3170,14 @@ bool bs_shape_ok(const Args& a, int64_t npad, int epi, int h3) {
   return true;
 }
 bool use_bs(const Args& a, int64_t npad, int epi, int h3) {
-  static const bool off = [] {
-    const char* e = getenv("MOLCLR_GEMM_BS");
-    return e != nullptr && e[0] == '0';
-  }();
+  static const bool off = env_is("MOLCLR_GEMM_BS", '0');
   if (g_bs_force == 1 || (off && g_bs_force < 2)) return false;
   return bs_shape_ok(a, npad, epi, h3);
 }
 // k_gemm_bs16 (default) or k_gemm_bs: MOLCLR_GEMM_BS16=0 or g_bs_force 2
 // (molclr_gemm_f32_h3_impl 2) takes the 32 x 32 x 16 form, g_bs_force 3 bs16
 bool use_bs16() {
-  static const bool off = [] {
-    const char* e = getenv("MOLCLR_GEMM_BS16");
-    return e != nullptr && e[0] == '0';
-  }();
+  static const bool off = env_is("MOLCLR_GEMM_BS16", '0');
   return g_bs_force == 3 || (g_bs_force != 2 && !off);
 }
 template <int EPI, int H3>
@@ -3198,38 +3188,12 @@ void launch_bs(const Args& a, int64_t npad, hipStream_t s) {
   // three waves per SIMD (<= 168 VGPRs): the c2 step 187.1k molecules/s
   // against 186.1k at two (MOLCLR_BS16_WAVES=8) and 180.8k on k_gemm_bs
   // (same box, round 6)
-  static const int w16 = [] {
-    const char* e = getenv("MOLCLR_BS16_WAVES");
-    return e != nullptr && atoi(e) == 8 ? 8 : 12;
-  }();
-  if (use_bs16() && w16 == 12)
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bsn<EPI, H3, 10, true, 12>),
-                         dim3((unsigned)(ntn * groups)), dim3(768), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate, a.amax,
-                         a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out, a.bits_in,
-                         a.bits_ld, ntn, groups);
-  else if (use_bs16())
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bsn<EPI, H3, 10, true>),
-                         dim3((unsigned)(ntn * groups)), dim3(512), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate, a.amax,
-                         a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out, a.bits_in,
-                         a.bits_ld, ntn, groups);
-  else
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bs<EPI, H3, 10, true>),
-                         dim3((unsigned)(ntn * groups)), dim3(512), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate, a.amax,
-                         a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out, a.bits_in,
-                         a.bits_ld, ntn, groups);
-}
-template <int H3>
-int dispatch_bs(int epi, const Args& a, int64_t npad, hipStream_t s) {
-  switch (epi) {
-    case MOLCLR_EPI_NONE: launch_bs<MOLCLR_EPI_NONE, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS: launch_bs<MOLCLR_EPI_BIAS, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS_RELU: launch_bs<MOLCLR_EPI_BIAS_RELU, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_RELU_MASK: launch_bs<MOLCLR_EPI_RELU_MASK, H3>(a, npad, s); return 0;
-    default: return -1;
-  }
+  static const int w16 = env_int("MOLCLR_BS16_WAVES", 12) == 8 ? 8 : 12;
+  const int waves = use_bs16() ? w16 : 8;
+  auto kern = !use_bs16()  ? k_gemm_bs<EPI, H3, 10, true>
+              : waves == 12 ? k_gemm_bsn<EPI, H3, 10, true, 12>
+                            : k_gemm_bsn<EPI, H3, 10, true>;
+  launch_h3(kern, dim3((unsigned)(ntn * groups)), dim3(64 * waves), a, npad, s, ntn, groups);
 }
 // The K = 600 products (lin2 = a1 W2^T and dagg = dz1 W1 of the c2 layer,
 // N = 300) on k_gemm_bsn with 64-column tiles: K in (576, 608], N <= 320, no
@@ -3239,10 +3203,7 @@ int dispatch_bs(int epi, const Args& a, int64_t npad, hipStream_t s) {
 // (16 waves measured slower on another box), so 8 waves is the default;
 // MOLCLR_GEMM_BS64=0 keeps q6.
 bool use_bs64(const Args& a, int64_t npad, int epi, int h3) {
-  static const bool off = [] {
-    const char* e = getenv("MOLCLR_GEMM_BS64");
-    return e != nullptr && e[0] == '0';
-  }();
+  static const bool off = env_is("MOLCLR_GEMM_BS64", '0');
   if (g_bs_force == 1 || g_bs_force == 2 || (off && g_bs_force != 3)) return false;
   if (h3 == 0 || a.N > 320 || a.N <= 192 || a.K <= 576 || a.K > 608 || a.ldb != 608) return false;
   if (a.crow != nullptr || a.bits_out != nullptr) return false;
@@ -3258,39 +3219,12 @@ void launch_bs64(const Args& a, int64_t npad, hipStream_t s) {
   int groups = molclr::cu_count() / ntn;
   groups = groups < 1 ? 1 : groups;
   // MOLCLR_BS64_WAVES=12 / 16: three / four waves per SIMD (<= 128 VGPRs)
-  static const int wv = [] {
-    const char* e = getenv("MOLCLR_BS64_WAVES");
-    const int v = e != nullptr ? atoi(e) : 8;
-    return v == 16 || v == 12 ? v : 8;
-  }();
-  if (wv == 8)
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bsn<EPI, H3, 19, false, 8, 64>),
-                         dim3((unsigned)(ntn * groups)), dim3(512), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate,
-                         a.amax, a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out,
-                         a.bits_in, a.bits_ld, ntn, groups);
-  else if (wv == 16)
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bsn<EPI, H3, 19, false, 16, 64>),
-                         dim3((unsigned)(ntn * groups)), dim3(1024), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate,
-                         a.amax, a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out,
-                         a.bits_in, a.bits_ld, ntn, groups);
-  else
-    molclr::launch_timed(molclr::kTimeGemm, (k_gemm_bsn<EPI, H3, 19, false, 12, 64>),
-                         dim3((unsigned)(ntn * groups)), dim3(768), 0, s, a.A, a.Bp, a.C, a.M, a.N,
-                         a.K, a.lda, a.ldb, npad, a.ldc, a.bias, a.aux, a.ldaux, a.accumulate,
-                         a.amax, a.bmax, a.cmax, a.crow, a.amax_out, a.arow_parts, a.bits_out,
-                         a.bits_in, a.bits_ld, ntn, groups);
-}
-template <int H3>
-int dispatch_bs64(int epi, const Args& a, int64_t npad, hipStream_t s) {
-  switch (epi) {
-    case MOLCLR_EPI_NONE: launch_bs64<MOLCLR_EPI_NONE, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS: launch_bs64<MOLCLR_EPI_BIAS, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_BIAS_RELU: launch_bs64<MOLCLR_EPI_BIAS_RELU, H3>(a, npad, s); return 0;
-    case MOLCLR_EPI_RELU_MASK: launch_bs64<MOLCLR_EPI_RELU_MASK, H3>(a, npad, s); return 0;
-    default: return -1;
-  }
+  static const int env_wv = env_int("MOLCLR_BS64_WAVES", 8);
+  const int wv = env_wv == 16 || env_wv == 12 ? env_wv : 8;
+  auto kern = wv == 8    ? k_gemm_bsn<EPI, H3, 19, false, 8, 64>
+              : wv == 16 ? k_gemm_bsn<EPI, H3, 19, false, 16, 64>
+                         : k_gemm_bsn<EPI, H3, 19, false, 12, 64>;
+  launch_h3(kern, dim3((unsigned)(ntn * groups)), dim3(64 * wv), a, npad, s, ntn, groups);
 }
 // partial row-max arrays of an h3 product's C (crow): one per 128 columns for
 // the wide products (k_gemm_bs's tiles); pp / q6, whose tiles may be 160
@@ -3298,39 +3232,40 @@ int dispatch_bs64(int epi, const Args& a, int64_t npad, hipStream_t s) {
 int64_t crow_parts(int64_t N) { return N > 320 ? (N + kBN - 1) / kBN : q6_col_tiles(N); }
 
 int run_q6(const Args& a, int64_t npad, int epi, hipStream_t s, int h3 = 0) {
+  int rc;
+  const char* missing;  // the error text of an epilogue the chosen family lacks
   if (h3 != 0 && use_bs(a, npad, epi, h3)) {
-    const int rc = h3 == 2 ? dispatch_bs<2>(epi, a, npad, s) : dispatch_bs<1>(epi, a, npad, s);
-    if (rc) {
-      molclr::set_error("gemm_f32_h3: no bs kernel for epilogue %d", epi);
+    missing = "gemm_f32_h3: no bs kernel";
+    rc = with_epi(epi, [&](auto e) {
+      if (h3 == 2) launch_bs<decltype(e)::value, 2>(a, npad, s);
+      else launch_bs<decltype(e)::value, 1>(a, npad, s);
+    });
+  } else if (h3 != 0 && use_bs64(a, npad, epi, h3)) {
+    missing = "gemm_f32_h3: no bs64 kernel";
+    rc = with_epi(epi, [&](auto e) {
+      if (h3 == 2) launch_bs64<decltype(e)::value, 2>(a, npad, s);
+      else launch_bs64<decltype(e)::value, 1>(a, npad, s);
+    });
+  } else {
+    if (g_bs_force >= 2) {
+      molclr::set_error("gemm_f32_h3_impl: the bs kernel does not take this product");
       return MOLCLR_ERR_UNSUPPORTED;
     }
-    MOLCLR_LAUNCHED();
-    return MOLCLR_OK;
-  }
-  if (h3 != 0 && use_bs64(a, npad, epi, h3)) {
-    const int rc = h3 == 2 ? dispatch_bs64<2>(epi, a, npad, s) : dispatch_bs64<1>(epi, a, npad, s);
-    if (rc) {
-      molclr::set_error("gemm_f32_h3: no bs64 kernel for epilogue %d", epi);
-      return MOLCLR_ERR_UNSUPPORTED;
+    if (a.crow != nullptr && crow_parts(a.N) > q6_col_tiles(a.N)) {
+      const int64_t w = q6_col_tiles(a.N);
+      const hipError_t e = molclr::zero_async(
+          a.crow + w * a.M, (size_t)(crow_parts(a.N) - w) * a.M * sizeof(float), s);
+      if (e != hipSuccess) return (int)e;
     }
-    MOLCLR_LAUNCHED();
-    return MOLCLR_OK;
+    missing = "gemm_f32_bplanes: no q6 kernel";
+    rc = with_epi(epi, [&](auto e) {
+      if (h3 == 2) launch_q6_tn<decltype(e)::value, 2>(a, npad, s);
+      else if (h3 == 1) launch_q6_tn<decltype(e)::value, 1>(a, npad, s);
+      else launch_q6_tn<decltype(e)::value, 0>(a, npad, s);
+    });
   }
-  if (g_bs_force >= 2) {
-    molclr::set_error("gemm_f32_h3_impl: the bs kernel does not take this product");
-    return MOLCLR_ERR_UNSUPPORTED;
-  }
-  if (a.crow != nullptr && crow_parts(a.N) > q6_col_tiles(a.N)) {
-    const int64_t w = q6_col_tiles(a.N);
-    const hipError_t e = molclr::zero_async(a.crow + w * a.M,
-                                            (size_t)(crow_parts(a.N) - w) * a.M * sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int rc = h3 == 2   ? dispatch_q6_tn<2>(epi, a, npad, s)
-                 : h3 == 1 ? dispatch_q6_tn<1>(epi, a, npad, s)
-                           : dispatch_q6_tn<0>(epi, a, npad, s);
   if (rc) {
-    molclr::set_error("gemm_f32_bplanes: no q6 kernel for epilogue %d", epi);
+    molclr::set_error("%s for epilogue %d", missing, epi);
     return MOLCLR_ERR_UNSUPPORTED;
   }
   MOLCLR_LAUNCHED();
@@ -3475,23 +3410,11 @@ int run_gemm(const Args& a0, int impl, bool bp, int a_kmajor, int b_kmajor, int 
       const int64_t ldc = a.ldc, ldaux = a.ldaux;
       const float *bias = a.bias, *aux = a.aux;
       const int accumulate = a.accumulate;
-      switch (epilogue) {
-        case MOLCLR_EPI_NONE:
-          molclr::launch_timed(molclr::kTimeGemm, k_splitk_reduce<MOLCLR_EPI_NONE>, g, dim3(256), 0, s,
-                               partial, sp, M, N, C, ldc, bias, aux, ldaux, accumulate, cs_partial, sp, a.colsum);
-          break;
-        case MOLCLR_EPI_BIAS:
-          molclr::launch_timed(molclr::kTimeGemm, k_splitk_reduce<MOLCLR_EPI_BIAS>, g, dim3(256), 0, s,
-                               partial, sp, M, N, C, ldc, bias, aux, ldaux, accumulate, cs_partial, sp, a.colsum);
-          break;
-        case MOLCLR_EPI_BIAS_RELU:
-          molclr::launch_timed(molclr::kTimeGemm, k_splitk_reduce<MOLCLR_EPI_BIAS_RELU>, g, dim3(256), 0,
-                               s, partial, sp, M, N, C, ldc, bias, aux, ldaux, accumulate, cs_partial, sp, a.colsum);
-          break;
-        default:
-          molclr::launch_timed(molclr::kTimeGemm, k_splitk_reduce<MOLCLR_EPI_RELU_MASK>, g, dim3(256), 0,
-                               s, partial, sp, M, N, C, ldc, bias, aux, ldaux, accumulate, cs_partial, sp, a.colsum);
-      }
+      rc = with_epi(epilogue, [&](auto e) {
+        molclr::launch_timed(molclr::kTimeGemm, k_splitk_reduce<decltype(e)::value>, g, dim3(256), 0,
+                             s, partial, sp, M, N, C, ldc, bias, aux, ldaux, accumulate, cs_partial,
+                             sp, a.colsum);
+      });
     }
   }
   if (rc != 0) {
@@ -4002,10 +3925,7 @@ int64_t w6_area(int64_t M, int64_t N) {
   return ((M + kW6BM - 1) / kW6BM * kW6BM) * ((N + bn - 1) / bn * bn);
 }
 bool w6_transposed(int64_t n_out, int64_t n_in) {
-  static const bool off = [] {
-    const char* e = getenv("MOLCLR_W6_TRANSPOSE");
-    return e != nullptr && e[0] == '0';
-  }();
+  static const bool off = env_is("MOLCLR_W6_TRANSPOSE", '0');
   return !off && w6_area(n_in, n_out) < w6_area(n_out, n_in);
 }
 // the w6 partial bytes of dW [n_out][n_in] (its chosen orientation)

@@ -1389,10 +1389,7 @@ using molclr::cu_count;
 // 97.8 -> 99.7, plain 71.6 -> 74.0 us: four times the cache lines per store
 // instruction), which keep the LDS transpose.  MOLCLR_TP_SWAP=0 disables it.
 static bool tp_swap() {
-  static const bool on = [] {
-    const char* e = getenv("MOLCLR_TP_SWAP");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = !env_is("MOLCLR_TP_SWAP", '0');
   return on;
 }
 

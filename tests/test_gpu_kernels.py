@@ -1199,6 +1199,40 @@ def _wave_pairs(A):
     return out
 
 
+def _h3_bs_inputs(lib, dev, M, N, K, scales, seed, edit_a=None):
+    """The inputs of a bs-kernel test, drawn from one generator seeded `seed`:
+    A with row magnitudes spread over six decades (edit_a, when given, changes
+    it in place before anything else is drawn), W, bias, the ReLU mask and its
+    words on the device, W's h3 planes, A's scales in the form `scales`
+    ("tensor": a max slot, "rows": one array of row maxima, "pairs": per-wave
+    pairs) with the matching a_row_parts, and the C to accumulate into."""
+    g = torch.Generator().manual_seed(seed)
+    A = torch.randn(M, K, generator=g) * torch.pow(10.0, -6 * torch.rand(M, 1, generator=g))
+    if edit_a is not None:
+        edit_a(A)
+    W = (torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5
+    bias = torch.randn(N, generator=g) * 0.1
+    mask = torch.rand(M, N, generator=g) > 0.4
+    words = (N + 31) // 32
+    pos = torch.zeros(M, words * 32, dtype=torch.bool)
+    pos[:, :N] = mask
+    mb = ((pos.view(M, words, 32).long() << torch.arange(32)).sum(-1).remainder(1 << 32).t()
+          .contiguous())
+    mb = torch.where(mb >= (1 << 31), mb - (1 << 32), mb).to(torch.int32).to(dev)
+    Ad, Wd, bd = A.to(dev), W.to(dev), bias.to(dev)
+    planes = _h3_planes(lib, Wd, N, K, 0, dev)
+    if scales == "tensor":
+        amax, parts = torch.zeros(2048, device=dev), 0
+        assert lib.molclr_absmax_f32(Ad.data_ptr(), M, K, K, amax.data_ptr(), 0,
+                                     ops._stream(Ad)) == 0
+    elif scales == "rows":
+        amax, parts = Ad.abs().amax(1).contiguous(), 1
+    else:
+        amax, parts = _wave_pairs(A).to(dev), -(K // 4)
+    C0 = torch.randn(M, N, generator=g).to(dev)
+    return A, W, bias, mask, words, mb, Ad, bd, planes, amax, parts, C0
+
+
 @pytest.mark.parametrize("M,N,K", [(30556, 600, 300), (1000, 400, 292), (70, 600, 300),
                                    (4099, 512, 300)])
 @pytest.mark.parametrize("scales", ["tensor", "rows", "pairs"])
@@ -1213,30 +1247,10 @@ def test_gemm_h3_bs_matches_pp(dev, M, N, K, scales, epi, acc):
     if scales == "pairs" and (K // 4 < 64 or M * (K // 4) > 400_000):
         pytest.skip("pairs: a dense A of >= 64 float4s per row; host-built for small M")
     lib = _lib.load()
-    g = torch.Generator().manual_seed(M + N + K + epi)
-    A = torch.randn(M, K, generator=g) * torch.pow(10.0, -6 * torch.rand(M, 1, generator=g))
-    W = (torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5
-    bias = torch.randn(N, generator=g) * 0.1
-    mask = torch.rand(M, N, generator=g) > 0.4
-    words = (N + 31) // 32
-    pos = torch.zeros(M, words * 32, dtype=torch.bool)
-    pos[:, :N] = mask
-    mb = ((pos.view(M, words, 32).long() << torch.arange(32)).sum(-1).remainder(1 << 32).t()
-          .contiguous())
-    mb = torch.where(mb >= (1 << 31), mb - (1 << 32), mb).to(torch.int32).to(dev)
-    Ad, Wd, bd = A.to(dev), W.to(dev), bias.to(dev)
-    planes = _h3_planes(lib, Wd, N, K, 0, dev)
+    A, W, bias, mask, words, mb, Ad, bd, planes, amax, parts, C0 = _h3_bs_inputs(
+        lib, dev, M, N, K, scales, M + N + K + epi)
     P = int(lib.molclr_gemm_row_parts(N))
     assert P == (N + 127) // 128
-    if scales == "tensor":
-        amax, parts = torch.zeros(2048, device=dev), 0
-        assert lib.molclr_absmax_f32(Ad.data_ptr(), M, K, K, amax.data_ptr(), 0,
-                                     ops._stream(Ad)) == 0
-    elif scales == "rows":
-        amax, parts = Ad.abs().amax(1).contiguous(), 1
-    else:
-        amax, parts = _wave_pairs(A).to(dev), -(K // 4)
-    C0 = torch.randn(M, N, generator=g).to(dev)
     outs = []
     for impl in (1, 2):
         C = C0.clone()
@@ -1296,29 +1310,9 @@ def test_gemm_h3_bs16(dev, M, N, K, scales, epi, acc):
     if scales == "pairs" and (K // 4 < 64 or M * (K // 4) > 400_000):
         pytest.skip("pairs: a dense A of >= 64 float4s per row; host-built for small M")
     lib = _lib.load()
-    g = torch.Generator().manual_seed(M + N + K + epi + 1)
-    A = torch.randn(M, K, generator=g) * torch.pow(10.0, -6 * torch.rand(M, 1, generator=g))
-    W = (torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5
-    bias = torch.randn(N, generator=g) * 0.1
-    mask = torch.rand(M, N, generator=g) > 0.4
-    words = (N + 31) // 32
-    pos = torch.zeros(M, words * 32, dtype=torch.bool)
-    pos[:, :N] = mask
-    mb = ((pos.view(M, words, 32).long() << torch.arange(32)).sum(-1).remainder(1 << 32).t()
-          .contiguous())
-    mb = torch.where(mb >= (1 << 31), mb - (1 << 32), mb).to(torch.int32).to(dev)
-    Ad, Wd, bd = A.to(dev), W.to(dev), bias.to(dev)
-    planes = _h3_planes(lib, Wd, N, K, 0, dev)
+    A, W, bias, mask, words, mb, Ad, bd, planes, amax, parts, C0 = _h3_bs_inputs(
+        lib, dev, M, N, K, scales, M + N + K + epi + 1)
     P = int(lib.molclr_gemm_row_parts(N))
-    if scales == "tensor":
-        amax, parts = torch.zeros(2048, device=dev), 0
-        assert lib.molclr_absmax_f32(Ad.data_ptr(), M, K, K, amax.data_ptr(), 0,
-                                     ops._stream(Ad)) == 0
-    elif scales == "rows":
-        amax, parts = Ad.abs().amax(1).contiguous(), 1
-    else:
-        amax, parts = _wave_pairs(A).to(dev), -(K // 4)
-    C0 = torch.randn(M, N, generator=g).to(dev)
     C = C0.clone()
     crow = torch.full((P, M), 7.0, device=dev)
     cmax = torch.zeros(2048, device=dev)
@@ -1382,34 +1376,17 @@ def test_gemm_h3_bs64(dev, M, N, K, scales, epi, acc):
     row's waves."""
     from molclr_amd import _lib
     lib = _lib.load()
-    g = torch.Generator().manual_seed(M + N + K + epi + 2)
-    A = torch.randn(M, K, generator=g) * torch.pow(10.0, -6 * torch.rand(M, 1, generator=g))
-    if scales == "pairs":
-        d4 = K // 4
-        s0 = torch.arange(M) * d4
-        four = ((s0 + d4 - 1) // 64 - s0 // 64) == 3
-        assert four.sum() >= M // 5  # the rows that start at unit >= 193 - d4 of a wave
-        A[four, K - 1] = A[four, :K - 4].abs().amax(1) * 2048.0
-    W = (torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5
-    bias = torch.randn(N, generator=g) * 0.1
-    mask = torch.rand(M, N, generator=g) > 0.4
-    words = (N + 31) // 32
-    pos = torch.zeros(M, words * 32, dtype=torch.bool)
-    pos[:, :N] = mask
-    mb = ((pos.view(M, words, 32).long() << torch.arange(32)).sum(-1).remainder(1 << 32).t()
-          .contiguous())
-    mb = torch.where(mb >= (1 << 31), mb - (1 << 32), mb).to(torch.int32).to(dev)
-    Ad, Wd, bd = A.to(dev), W.to(dev), bias.to(dev)
-    planes = _h3_planes(lib, Wd, N, K, 0, dev)
-    if scales == "tensor":
-        amax, parts = torch.zeros(2048, device=dev), 0
-        assert lib.molclr_absmax_f32(Ad.data_ptr(), M, K, K, amax.data_ptr(), 0,
-                                     ops._stream(Ad)) == 0
-    elif scales == "rows":
-        amax, parts = Ad.abs().amax(1).contiguous(), 1
-    else:
-        amax, parts = _wave_pairs(A).to(dev), -(K // 4)
-    C0 = torch.randn(M, N, generator=g).to(dev)
+
+    def four_wave_rows(A):
+        if scales == "pairs":
+            d4 = K // 4
+            s0 = torch.arange(M) * d4
+            four = ((s0 + d4 - 1) // 64 - s0 // 64) == 3
+            assert four.sum() >= M // 5  # the rows that start at unit >= 193 - d4 of a wave
+            A[four, K - 1] = A[four, :K - 4].abs().amax(1) * 2048.0
+
+    A, W, bias, mask, words, mb, Ad, bd, planes, amax, parts, C0 = _h3_bs_inputs(
+        lib, dev, M, N, K, scales, M + N + K + epi + 2, edit_a=four_wave_rows)
     C = C0.clone()
     cmax = torch.zeros(2048, device=dev)
     aout = torch.zeros(2048, device=dev)
