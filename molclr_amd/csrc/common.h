@@ -203,36 +203,48 @@ inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipStream
 // norm.hip: BatchNorm workspace for any split of `rows` into segments
 size_t molclr_batchnorm_ws_bound(int64_t rows, int64_t D);
 
+namespace molclr {
+// norm.hip: the segmented BatchNorm behind every molclr_batchnorm_* entry
+// point and the encoder executors.  What every call has:
+struct BnSegs {
+  const char* who;              // the caller, named in a dtype or row-maxima refusal
+  int nseg;
+  const int64_t* seg_rows;      // host-sized segments, or
+  const int64_t* seg_rows_dev;  // device-sized ones (on the device), rows_cap rows in all
+  int64_t rows_cap;
+  int64_t D;
+  int dtype;
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t stream;
+  const DropArgs* drop;  // the dropout after the BatchNorm (dropout.h); NULL: none
+};
+struct BnFwdArgs : BnSegs {
+  const void* z;
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  int64_t* nbt;
+  void* y;  // NULL: statistics and coefficients only
+  float *save_mean, *save_invstd;
+  float* coeffs;  // scale, shift [nseg][D] left here; NULL: in the workspace
+  double momentum, eps;
+  int training, relu;
+};
+struct BnBwdArgs : BnSegs {
+  const void *dy, *z;  // with dropout: dy the gradient behind it
+  const float *gamma, *beta, *save_mean, *save_invstd;
+  void* dz;
+  float *dgamma, *dbeta;
+  int relu, accumulate;
+  float *rowmax, *slot;  // fp32: dz's row maxima and max slot (the h3 scales), or NULL
+  int frozen;  // save_mean / save_invstd: the running statistics an eval forward saved
+};
+int bn_forward(const BnFwdArgs& a);
+int bn_backward(const BnBwdArgs& a);
+
 // The encoder executors' kernels with dropout after the BatchNorm (dropout.h;
 // the public entry points keep their signatures and run without it).
 // Segments: host-sized (seg_rows) or device-sized (seg_rows_dev, rows_cap).
-namespace molclr {
-// norm.hip: molclr_batchnorm_seg_fwd / _fwd_dev, the stored y dropped
-int batchnorm_seg_fwd_drop(const void* z, const float* gamma, const float* beta,
-                           float* running_mean, float* running_var, int64_t* num_batches_tracked,
-                           void* y, float* save_mean, float* save_invstd, int nseg,
-                           const int64_t* seg_rows, const int64_t* seg_rows_dev, int64_t rows_cap,
-                           int64_t D, int dtype, double momentum, double eps, int training,
-                           int relu, const DropArgs& drop, void* workspace, size_t workspace_bytes,
-                           hipStream_t s);
-// norm.hip: molclr_batchnorm_seg_bwd / _bwd_max / _bwd_dev, dy the gradient
-// behind the dropout
-int batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* gamma, const float* beta,
-                           const float* save_mean, const float* save_invstd, void* dz,
-                           float* dgamma, float* dbeta, int nseg, const int64_t* seg_rows,
-                           const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D, int dtype,
-                           int relu, int accumulate, float* rowmax, float* slot,
-                           const DropArgs& drop, void* workspace, size_t workspace_bytes,
-                           hipStream_t s);
-// the backward through frozen statistics (molclr_batchnorm_seg_bwd_frozen*),
-// host- or device-sized segments; drop: the dropout after it (NULL: none)
-int batchnorm_seg_bwd_frozen_drop(const void* dy, const void* z, const float* gamma,
-                                  const float* beta, const float* save_mean,
-                                  const float* save_invstd, void* dz, float* dgamma, float* dbeta,
-                                  int nseg, const int64_t* seg_rows, const int64_t* seg_rows_dev,
-                                  int64_t rows_cap, int64_t D, int dtype, int relu, int accumulate,
-                                  float* rowmax, float* slot, const DropArgs* drop,
-                                  void* workspace, size_t workspace_bytes, hipStream_t s);
 // aggregate.hip: molclr_gine_aggregate_bn_fwd / _bf16, every source element
 // dropped after the BatchNorm (+ReLU), before the bf16 rounding
 int gine_aggregate_bn_fwd_drop(const void* z, const float* coeffs, int relu, int nseg,
@@ -374,6 +386,15 @@ struct StBF16 {
     p[i] = (uint16_t)(f32x2_to_bf16x2(v, 0.f) & 0xFFFFu);
   }
 };
+
+// Runtime dtype to storage type: the status of fn(StF32{}) or fn(StBF16{}),
+// any other dtype refused in the name of `who`.
+template <typename F>
+int with_storage(int dtype, const char* who, F&& fn) {
+  if (dtype == MOLCLR_DTYPE_F32) return fn(StF32{});
+  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "%s: dtype %d", who, dtype);
+  return fn(StBF16{});
+}
 
 // ---------------------------------------------------------------------------
 // Row segments (norm.hip's segmented BatchNorm; aggregate.hip's BatchNorm

@@ -161,37 +161,34 @@ int graph_segments(const molclr_device_graph* g, const int64_t* N, SegRows& out)
   return MOLCLR_OK;
 }
 
-// the segmented BatchNorm of a graph, host- or device-sized; drop: the dropout
-// after it (NULL: none)
+// the segmented BatchNorm of a graph, host- or device-sized (molclr::bn_forward
+// / bn_backward); drop: the dropout after it (NULL: none).  `who`: the entry
+// point of norm.hip that makes the same call, which a refusal names.
+molclr::BnSegs bn_segs(const SegRows& sg, const char* who, int64_t D, int dtype,
+                       const DropArgs* drop, void* ws, size_t ws_bytes, molclr_stream_t stream) {
+  return {who, sg.n, sg.rows, sg.dev, sg.cap, D, dtype, ws, ws_bytes, molclr::as_stream(stream),
+          drop};
+}
 int seg_bn_fwd(const SegRows& sg, const void* z, const float* gamma, const float* beta,
                float* rmean, float* rvar, int64_t* nbt, void* y, float* mean, float* invstd,
                int64_t D, int dtype, double momentum, double eps, int training, int relu,
                const DropArgs* drop, void* ws, size_t ws_bytes, molclr_stream_t stream) {
-  if (drop)
-    return molclr::batchnorm_seg_fwd_drop(z, gamma, beta, rmean, rvar, nbt, y, mean, invstd, sg.n,
-                                          sg.rows, sg.dev, sg.cap, D, dtype, momentum, eps,
-                                          training, relu, *drop, ws, ws_bytes,
-                                          molclr::as_stream(stream));
-  if (sg.dev)
-    return molclr_batchnorm_seg_fwd_dev(z, gamma, beta, rmean, rvar, nbt, y, mean, invstd, sg.n,
-                                        sg.dev, sg.cap, D, dtype, momentum, eps, training, relu,
-                                        ws, ws_bytes, stream);
-  return molclr_batchnorm_seg_fwd(z, gamma, beta, rmean, rvar, nbt, y, mean, invstd, sg.n,
-                                  sg.rows, D, dtype, momentum, eps, training, relu, ws, ws_bytes,
-                                  stream);
+  const char* who = drop     ? "batchnorm_seg_fwd_drop"
+                    : sg.dev ? "batchnorm_seg_fwd_dev"
+                             : "batchnorm_seg_fwd";
+  return molclr::bn_forward({bn_segs(sg, who, D, dtype, drop, ws, ws_bytes, stream), z, gamma,
+                             beta, rmean, rvar, nbt, y, mean, invstd, nullptr, momentum, eps,
+                             training, relu});
 }
 // its statistics and apply coefficients only (coef: scale, shift [sg.n][D])
 int seg_bn_coeffs(const SegRows& sg, const void* z, const float* gamma, const float* beta,
                   float* rmean, float* rvar, int64_t* nbt, float* mean, float* invstd, float* coef,
                   int64_t D, int dtype, double momentum, double eps, int training, void* ws,
                   size_t ws_bytes, molclr_stream_t stream) {
-  if (sg.dev)
-    return molclr_batchnorm_seg_coeffs_dev(z, gamma, beta, rmean, rvar, nbt, mean, invstd, coef,
-                                           sg.n, sg.dev, sg.cap, D, dtype, momentum, eps, training,
-                                           ws, ws_bytes, stream);
-  return molclr_batchnorm_seg_coeffs(z, gamma, beta, rmean, rvar, nbt, mean, invstd, coef, sg.n,
-                                     sg.rows, D, dtype, momentum, eps, training, ws, ws_bytes,
-                                     stream);
+  const char* who = sg.dev ? "batchnorm_seg_coeffs_dev" : "batchnorm_seg_coeffs";
+  return molclr::bn_forward({bn_segs(sg, who, D, dtype, nullptr, ws, ws_bytes, stream), z, gamma,
+                             beta, rmean, rvar, nbt, nullptr, mean, invstd, coef, momentum, eps,
+                             training, 0});
 }
 // rowmax != NULL (fp32): also dz's row maxima and max slot (the h3 scales)
 // frozen: mean / invstd are the running statistics an eval-mode forward saved
@@ -200,26 +197,14 @@ int seg_bn_bwd(const SegRows& sg, int frozen, const void* dy, const void* z, con
                float* dbeta, int64_t D, int dtype, int relu, int accumulate, float* rowmax,
                float* slot, const DropArgs* drop, void* ws, size_t ws_bytes,
                molclr_stream_t stream) {
-  if (frozen)
-    return molclr::batchnorm_seg_bwd_frozen_drop(dy, z, gamma, beta, mean, invstd, dz, dgamma,
-                                                 dbeta, sg.n, sg.rows, sg.dev, sg.cap, D, dtype,
-                                                 relu, accumulate, rowmax, slot, drop, ws, ws_bytes,
-                                                 molclr::as_stream(stream));
-  if (drop)
-    return molclr::batchnorm_seg_bwd_drop(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta,
-                                          sg.n, sg.rows, sg.dev, sg.cap, D, dtype, relu,
-                                          accumulate, rowmax, slot, *drop, ws, ws_bytes,
-                                          molclr::as_stream(stream));
-  if (sg.dev)
-    return molclr_batchnorm_seg_bwd_dev(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta, sg.n,
-                                        sg.dev, sg.cap, D, dtype, relu, accumulate, rowmax, slot,
-                                        ws, ws_bytes, stream);
-  if (rowmax)
-    return molclr_batchnorm_seg_bwd_max((const float*)dy, (const float*)z, gamma, beta, mean,
-                                        invstd, (float*)dz, dgamma, dbeta, sg.n, sg.rows, D, relu,
-                                        accumulate, rowmax, slot, ws, ws_bytes, stream);
-  return molclr_batchnorm_seg_bwd(dy, z, gamma, beta, mean, invstd, dz, dgamma, dbeta, sg.n,
-                                  sg.rows, D, dtype, relu, accumulate, ws, ws_bytes, stream);
+  const char* who = frozen   ? "batchnorm_seg_bwd_frozen"
+                    : drop   ? "batchnorm_seg_bwd_drop"
+                    : sg.dev ? "batchnorm_seg_bwd_dev"
+                    : rowmax ? "batchnorm_seg_bwd_max"
+                             : "batchnorm_seg_bwd";
+  return molclr::bn_backward({bn_segs(sg, who, D, dtype, drop, ws, ws_bytes, stream), dy, z, gamma,
+                              beta, mean, invstd, dz, dgamma, dbeta, relu, accumulate, rowmax,
+                              slot, frozen});
 }
 
 // This call's dropout: the key in the arena, opened by the forward

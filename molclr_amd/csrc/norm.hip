@@ -1023,140 +1023,141 @@ MOLCLR_API int molclr_colsum_f32(const float* X, float* out, int64_t rows, int64
                             molclr::as_stream(stream));
 }
 
+// ---------------------------------------------------------------------------
+// BatchNorm, host side: one plan, one workspace layout, one forward and one
+// backward (molclr::bn_forward / bn_backward, common.h) behind every
+// molclr_batchnorm_* entry point and the encoder executors.
+// ---------------------------------------------------------------------------
 namespace {
+
+using molclr::BnBwdArgs;
+using molclr::BnFwdArgs;
+using molclr::BnSegs;
 
 // host-side segment plan: partitions of every segment exactly as a one-segment
 // call over its rows would have them.  Device-sized (drows != NULL): the
 // segments' rows are read on the device, `cap` rows in all; P covers any
 // split of cap rows into nseg segments (spare partitions exit at once).
-int make_segs(int nseg, const int64_t* seg_rows, const int64_t* drows, int64_t cap, int64_t D,
-              Segs& sg, int64_t& P, int64_t& rows) {
+struct BnPlan {
+  Segs sg;
+  molclr::Band b;
+  int64_t P, rows;
+};
+int make_plan(int nseg, const int64_t* seg_rows, const int64_t* drows, int64_t cap, int64_t D,
+              BnPlan& p) {
   MOLCLR_REQUIRE(nseg >= 1 && nseg <= MOLCLR_MAX_SEGMENTS && (seg_rows || drows),
                  "batchnorm: %d segments (1..%d)", nseg, MOLCLR_MAX_SEGMENTS);
   MOLCLR_REQUIRE(molclr::band_dim_ok(D), "batchnorm: dim %lld must be a multiple of 4 in [4, %lld]",
                  (long long)D, (long long)molclr::kBandMaxDim);
-  const molclr::Band b = molclr::make_band(D);
+  p.b = molclr::make_band(D);
+  Segs& sg = p.sg;
   sg.n = nseg;
-  sg.band = b.band;
+  sg.band = p.b.band;
   sg.drows = drows;
-  P = 0;
-  rows = 0;
+  p.P = 0;
+  p.rows = 0;
   for (int s = 0; s < MOLCLR_MAX_SEGMENTS; ++s) sg.rows[s] = 0;
   if (drows) {
     MOLCLR_REQUIRE(cap >= 0, "batchnorm: negative row capacity");
-    P = band_parts_bound(cap, b.band, nseg);
-    rows = cap;
+    p.P = band_parts_bound(cap, p.b.band, nseg);
+    p.rows = cap;
     return MOLCLR_OK;
   }
   for (int s = 0; s < nseg; ++s) {
     MOLCLR_REQUIRE(seg_rows[s] >= 0, "batchnorm: negative segment rows");
     sg.rows[s] = seg_rows[s];
-    P += band_parts(seg_rows[s], b.band);
-    rows += seg_rows[s];
+    p.P += band_parts(seg_rows[s], p.b.band);
+    p.rows += seg_rows[s];
   }
   return MOLCLR_OK;
 }
+int make_plan(const BnSegs& a, BnPlan& p) {
+  return make_plan(a.nseg, a.seg_rows, a.seg_rows_dev, a.rows_cap, a.D, p);
+}
 
+// the workspace of every BatchNorm call, forward or backward
+struct BnWs {
+  float *pmean, *pm2;   // [P][D] partial mean, m2 (backward: partial s1, s2)
+  float* pn;            // [P] partial n
+  float *scale, *shift; // [nseg][D] apply coefficients
+  float *k1, *k2;       // [nseg][D] the backward's per-column terms
+  BnWs(molclr::Workspace& w, int64_t P, int64_t D, int nseg)
+      : pmean(w.take<float>(P * D)),
+        pm2(w.take<float>(P * D)),
+        pn(w.take<float>(P)),
+        scale(w.take<float>(nseg * D)),
+        shift(w.take<float>(nseg * D)),
+        k1(w.take<float>(nseg * D)),
+        k2(w.take<float>(nseg * D)) {}
+};
 size_t bn_ws_bytes(int64_t P, int64_t D, int nseg) {
   molclr::Workspace w(nullptr, 0);
-  w.take<float>(P * D);     // partial mean / s1
-  w.take<float>(P * D);     // partial m2 / s2
-  w.take<float>(P);         // partial n
-  w.take<float>(nseg * D);  // scale
-  w.take<float>(nseg * D);  // shift
-  w.take<float>(nseg * D);  // k1
-  w.take<float>(nseg * D);  // k2
+  BnWs(w, P, D, nseg);
   return w.used + 256;
 }
 
-// The forward up to the apply: batch statistics (training) or the running
-// ones (eval), save_mean / save_invstd, the running-statistics update, and the
-// apply coefficients scale / shift [nseg][D] -- at `coeffs` (scale, then
-// shift) when given, else in the workspace.  `plan` returns the segment plan
-// and the coefficients for the apply.
-struct BnPlan {
-  Segs sg;
-  int64_t rows;
-  const float *scale, *shift;
-};
-template <typename St>
-int bn_fwd_coeffs(const void* zv, const float* gamma, const float* beta, float* running_mean,
-                  float* running_var, int64_t* nbt, float* save_mean, float* save_invstd,
-                  float* coeffs, int nseg, const int64_t* seg_rows, int64_t D, double momentum,
-                  double eps, int training, void* workspace, size_t workspace_bytes, hipStream_t s,
-                  const int64_t* drows, int64_t cap, BnPlan& plan) {
-  Segs& sg = plan.sg;
-  int64_t P = 0, rows = 0;
-  if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
-  for (int q = 0; q < nseg && !drows; ++q)  // device-sized: the caller's contract
-    MOLCLR_REQUIRE(!training || seg_rows[q] > 1,
-                   "batchnorm_fwd: need more than 1 row per segment when training");
-  MOLCLR_REQUIRE(training || (running_mean && running_var), "batchnorm_fwd: eval needs running stats");
-  MOLCLR_REQUIRE(save_mean && save_invstd && (rows == 0 || zv), "batchnorm_fwd: null pointer");
-  MOLCLR_REQUIRE_WS(workspace_bytes, bn_ws_bytes(P, D, nseg));
-  const auto* z = static_cast<const typename St::T*>(zv);
-  const molclr::Band b = molclr::make_band(D);
-  molclr::Workspace w(workspace, workspace_bytes);
-  float* pmean = w.take<float>(P * D);
-  float* pm2 = w.take<float>(P * D);
-  float* pn = w.take<float>(P);
-  float* scale = w.take<float>(nseg * D);
-  float* shift = w.take<float>(nseg * D);
-  if (coeffs) {
-    scale = coeffs;
-    shift = coeffs + (size_t)nseg * D;
-  }
-  if (training) {
-    const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
-    hipLaunchKernelGGL(k_bn_stats_partial<St>, dim3((unsigned)P), dim3(b.threads), lds, s, z, b.d4,
-                       b.band, sg, (float4*)pmean, (float4*)pm2, pn);
-    hipLaunchKernelGGL(k_bn_stats_final, dim3(molclr::ceil_div(D, kRedCols)),
-                       dim3(kRedCols * kRedLanes), 0, s, pmean, pm2, pn, sg, D, gamma, beta,
-                       running_mean, running_var, save_mean, save_invstd, scale, shift,
-                       (float)momentum, (float)eps, nbt);
-  } else {
-    hipLaunchKernelGGL(k_bn_eval_coeffs, dim3(molclr::ceil_div(D, kT)), dim3(kT), 0, s, gamma,
-                       beta, running_mean, running_var, D, nseg, (float)eps, save_mean,
-                       save_invstd, scale, shift);
-  }
-  plan.rows = rows;
-  plan.scale = scale;
-  plan.shift = shift;
-  MOLCLR_LAUNCHED();
-  return MOLCLR_OK;
+// NoDrop, or the call's dropout
+template <typename F>
+void with_drop(const DropArgs* drop, F&& fn) {
+  if (drop) fn(*drop);
+  else fn(NoDrop{});
 }
 
+// The forward: batch statistics (training) or the running ones (eval),
+// save_mean / save_invstd, the running-statistics update, and the apply
+// coefficients scale / shift [nseg][D] -- at a.coeffs (scale, then shift) when
+// given, else in the workspace; then the apply, unless y == NULL (statistics
+// only: the consumer applies the coefficients).
 template <typename St>
-int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running_mean,
-           float* running_var, int64_t* nbt, void* yv, float* save_mean, float* save_invstd,
-           int nseg, const int64_t* seg_rows, int64_t D, double momentum, double eps, int training,
-           int relu, void* workspace, size_t workspace_bytes, hipStream_t s,
-           const int64_t* drows = nullptr, int64_t cap = 0, const DropArgs* drop = nullptr) {
-  BnPlan plan;
-  if (int rc = bn_fwd_coeffs<St>(zv, gamma, beta, running_mean, running_var, nbt, save_mean,
-                                 save_invstd, nullptr, nseg, seg_rows, D, momentum, eps, training,
-                                 workspace, workspace_bytes, s, drows, cap, plan))
-    return rc;
-  const auto* z = static_cast<const typename St::T*>(zv);
-  auto* y = static_cast<typename St::T*>(yv);
-  const Segs& sg = plan.sg;
-  const float *scale = plan.scale, *shift = plan.shift;
-  const int64_t total4 = plan.rows * (D / 4);
-  if (total4 > 0 && y) {  // y == NULL: statistics only (the consumer applies them)
-    auto apply = [&](auto dr) {
-      using DR = decltype(dr);
-      if (St::kBytes == 2 && D % 8 == 0)
-        hipLaunchKernelGGL((k_bn_apply<St, 2, DR>), dim3(molclr::ceil_div(total4 / 2, kT)),
-                           dim3(kT), 0, s, z, (const float4*)scale, (const float4*)shift, y,
-                           total4, (int)(D / 4), relu, sg, dr);
-      else
-        hipLaunchKernelGGL((k_bn_apply<St, 1, DR>), dim3(molclr::ceil_div(total4, kT)), dim3(kT),
-                           0, s, z, (const float4*)scale, (const float4*)shift, y, total4,
-                           (int)(D / 4), relu, sg, dr);
-    };
-    if (drop) apply(*drop);
-    else apply(NoDrop{});
+int bn_forward_t(const BnFwdArgs& a) {
+  BnPlan p;
+  if (int rc = make_plan(a, p)) return rc;
+  const int64_t D = a.D;
+  const int nseg = a.nseg;
+  for (int q = 0; q < nseg && !a.seg_rows_dev; ++q)  // device-sized: the caller's contract
+    MOLCLR_REQUIRE(!a.training || a.seg_rows[q] > 1,
+                   "batchnorm_fwd: need more than 1 row per segment when training");
+  MOLCLR_REQUIRE(a.training || (a.running_mean && a.running_var),
+                 "batchnorm_fwd: eval needs running stats");
+  MOLCLR_REQUIRE(a.save_mean && a.save_invstd && (p.rows == 0 || a.z), "batchnorm_fwd: null pointer");
+  MOLCLR_REQUIRE_WS(a.workspace_bytes, bn_ws_bytes(p.P, D, nseg));
+  const auto* z = static_cast<const typename St::T*>(a.z);
+  auto* y = static_cast<typename St::T*>(a.y);
+  const molclr::Band& b = p.b;
+  const Segs& sg = p.sg;
+  hipStream_t s = a.stream;
+  molclr::Workspace w(a.workspace, a.workspace_bytes);
+  const BnWs ws(w, p.P, D, nseg);
+  float* scale = a.coeffs ? a.coeffs : ws.scale;
+  float* shift = a.coeffs ? a.coeffs + (size_t)nseg * D : ws.shift;
+  if (a.training) {
+    const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
+    hipLaunchKernelGGL(k_bn_stats_partial<St>, dim3((unsigned)p.P), dim3(b.threads), lds, s, z,
+                       b.d4, b.band, sg, (float4*)ws.pmean, (float4*)ws.pm2, ws.pn);
+    hipLaunchKernelGGL(k_bn_stats_final, dim3(molclr::ceil_div(D, kRedCols)),
+                       dim3(kRedCols * kRedLanes), 0, s, ws.pmean, ws.pm2, ws.pn, sg, D, a.gamma,
+                       a.beta, a.running_mean, a.running_var, a.save_mean, a.save_invstd, scale,
+                       shift, (float)a.momentum, (float)a.eps, a.nbt);
+  } else {
+    hipLaunchKernelGGL(k_bn_eval_coeffs, dim3(molclr::ceil_div(D, kT)), dim3(kT), 0, s, a.gamma,
+                       a.beta, a.running_mean, a.running_var, D, nseg, (float)a.eps, a.save_mean,
+                       a.save_invstd, scale, shift);
   }
+  MOLCLR_LAUNCHED();
+  const int64_t total4 = p.rows * (D / 4);
+  if (total4 == 0 || !y) return MOLCLR_OK;
+  const int relu = a.relu;
+  with_drop(a.drop, [&](auto dr) {
+    using DR = decltype(dr);
+    if (St::kBytes == 2 && D % 8 == 0)
+      hipLaunchKernelGGL((k_bn_apply<St, 2, DR>), dim3(molclr::ceil_div(total4 / 2, kT)), dim3(kT),
+                         0, s, z, (const float4*)scale, (const float4*)shift, y, total4,
+                         (int)(D / 4), relu, sg, dr);
+    else
+      hipLaunchKernelGGL((k_bn_apply<St, 1, DR>), dim3(molclr::ceil_div(total4, kT)), dim3(kT), 0,
+                         s, z, (const float4*)scale, (const float4*)shift, y, total4, (int)(D / 4),
+                         relu, sg, dr);
+  });
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
@@ -1164,138 +1165,107 @@ int bn_fwd(const void* zv, const float* gamma, const float* beta, float* running
 // waves a row of D / 4 float4s can touch (k_bn_bwd_apply's row parts)
 int bn_row_parts(int64_t D) { return (int)((D / 4 + 62) / 64) + 1; }
 
+// The backward.  Training: k_bn_bwd_partial, k_bn_bwd_final (dgamma / dbeta,
+// k1 / k2), then the apply, which recomputes the forward's coefficient
+// expression in-kernel (same ReLU mask).  Frozen (the eval forward's running
+// statistics saved per segment): k_bn_bwd_frozen writes dz with its partial
+// sums, then k_bn_bwd_final; a segment of one row is legal.  bf16 rows take
+// neither row maxima nor a slot (bn_backward refuses the maxima).
 template <typename St>
-int bn_bwd(const void* dyv, const void* zv, const float* gamma, const float* beta,
-           const float* save_mean, const float* save_invstd, void* dzv, float* dgamma,
-           float* dbeta, int nseg, const int64_t* seg_rows, int64_t D, int relu, int accumulate,
-           void* workspace, size_t workspace_bytes, hipStream_t s, float* rowparts = nullptr,
-           float* slot = nullptr, const int64_t* drows = nullptr, int64_t cap = 0,
-           const DropArgs* drop = nullptr) {
-  Segs sg;
-  int64_t P = 0, rows = 0;
-  if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
-  MOLCLR_REQUIRE(rows > 0 && dyv && zv && save_mean && save_invstd && dzv, "batchnorm_bwd: bad args");
-  for (int q = 0; q < nseg && !drows; ++q)
-    MOLCLR_REQUIRE(seg_rows[q] > 0, "batchnorm_bwd: empty segment");
-  MOLCLR_REQUIRE_WS(workspace_bytes, bn_ws_bytes(P, D, nseg));
-  const auto* dy = static_cast<const typename St::T*>(dyv);
-  const auto* z = static_cast<const typename St::T*>(zv);
-  auto* dz = static_cast<typename St::T*>(dzv);
-  const molclr::Band b = molclr::make_band(D);
-  molclr::Workspace w(workspace, workspace_bytes);
-  float* p1 = w.take<float>(P * D);
-  float* p2 = w.take<float>(P * D);
-  w.take<float>(P);
-  w.take<float>(nseg * D);  // scale
-  w.take<float>(nseg * D);  // shift
-  float* k1 = w.take<float>(nseg * D);
-  float* k2 = w.take<float>(nseg * D);
-  // the forward's coefficient expression is recomputed in-kernel (same ReLU mask)
+int bn_backward_t(const BnBwdArgs& a) {
+  BnPlan p;
+  if (int rc = make_plan(a, p)) return rc;
+  const char* fz = a.frozen ? "_frozen" : "";
+  const int64_t D = a.D, rows = p.rows;
+  MOLCLR_REQUIRE(rows > 0 && a.dy && a.z && a.save_mean && a.save_invstd && a.dz,
+                 "batchnorm_bwd%s: bad args", fz);
+  for (int q = 0; q < a.nseg && !a.seg_rows_dev; ++q)
+    MOLCLR_REQUIRE(a.seg_rows[q] > 0, "batchnorm_bwd%s: empty segment", fz);
+  MOLCLR_REQUIRE_WS(a.workspace_bytes, bn_ws_bytes(p.P, D, a.nseg));
+  float* rowparts = St::kBytes == 4 ? a.rowmax : nullptr;
+  float* slot = St::kBytes == 4 ? a.slot : nullptr;
+  static_assert(kT % 64 == 0, "row parts follow the waves");
+  MOLCLR_REQUIRE(!rowparts || rows < (1ll << 31), "batchnorm_seg_bwd%s_max: too many rows", fz);
+  const auto* dy = static_cast<const typename St::T*>(a.dy);
+  const auto* z = static_cast<const typename St::T*>(a.z);
+  auto* dz = static_cast<typename St::T*>(a.dz);
+  const auto* mean = (const float4*)a.save_mean;
+  const auto* invstd = (const float4*)a.save_invstd;
+  const float *gamma = a.gamma, *beta = a.beta;
+  const int relu = a.relu;
+  const molclr::Band& b = p.b;
+  const Segs& sg = p.sg;
+  hipStream_t s = a.stream;
+  molclr::Workspace w(a.workspace, a.workspace_bytes);
+  const BnWs ws(w, p.P, D, a.nseg);
+  float *p1 = ws.pmean, *p2 = ws.pm2;
   const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
   const int64_t total4 = rows * (D / 4);
-  static_assert(kT % 64 == 0, "row parts follow the waves");
-  MOLCLR_REQUIRE(!rowparts || rows < (1ll << 31), "batchnorm_seg_bwd_max: too many rows");
-  auto launch = [&](auto dr) {
-    using DR = decltype(dr);
-    hipLaunchKernelGGL((k_bn_bwd_partial<St, DR>), dim3((unsigned)P), dim3(b.threads), lds, s, dy,
-                       z, (const float4*)save_mean, (const float4*)save_invstd, gamma, beta, b.d4,
-                       b.band, sg, relu, (float4*)p1, (float4*)p2, dr);
+  auto finish = [&] {
     hipLaunchKernelGGL(k_bn_bwd_final, dim3(molclr::ceil_div(D, kRedCols)),
-                       dim3(kRedCols * kRedLanes), 0, s, p1, p2, sg, D, dgamma, dbeta, k1, k2,
-                       accumulate);
+                       dim3(kRedCols * kRedLanes), 0, s, p1, p2, sg, D, a.dgamma, a.dbeta, ws.k1,
+                       ws.k2, a.accumulate);
+  };
+  with_drop(a.drop, [&](auto dr) {
+    using DR = decltype(dr);
+    if (a.frozen) {
+      auto go = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.P), dim3(threads), lds, s, dy, z, mean, invstd,
+                           gamma, beta, dz, b.d4, b.band, sg, rows, relu, (float4*)p1, (float4*)p2,
+                           rowparts, bn_row_parts(D), slot, dr);
+      };
+      if constexpr (St::kBytes == 4) {
+        if (rowparts) go(k_bn_bwd_frozen<St, 1, true, DR>, b.threads);
+        else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
+      } else {
+        if (D % 8 == 0) go(k_bn_bwd_frozen<St, 2, false, DR>, (b.band * (b.d4 / 2) + 63) / 64 * 64);
+        else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
+      }
+      finish();
+      return;
+    }
+    hipLaunchKernelGGL((k_bn_bwd_partial<St, DR>), dim3((unsigned)p.P), dim3(b.threads), lds, s, dy,
+                       z, mean, invstd, gamma, beta, b.d4, b.band, sg, relu, (float4*)p1,
+                       (float4*)p2, dr);
+    finish();
     if (St::kBytes == 2 && D % 8 == 0 && !rowparts && !slot)
       hipLaunchKernelGGL((k_bn_bwd_apply2<St, DR>), dim3(molclr::ceil_div(total4 / 2, kT)),
-                         dim3(kT), 0, s, dy, z, (const float4*)save_mean,
-                         (const float4*)save_invstd, gamma, beta, (const float4*)k1,
-                         (const float4*)k2, dz, total4, (int)(D / 4), relu, sg, dr);
+                         dim3(kT), 0, s, dy, z, mean, invstd, gamma, beta, (const float4*)ws.k1,
+                         (const float4*)ws.k2, dz, total4, (int)(D / 4), relu, sg, dr);
     else
       hipLaunchKernelGGL((k_bn_bwd_apply<St, DR>), dim3(molclr::ceil_div(total4, kT)), dim3(kT), 0,
-                         s, dy, z, (const float4*)save_mean, (const float4*)save_invstd, gamma,
-                         beta, (const float4*)k1, (const float4*)k2, dz, total4, (int)(D / 4),
-                         relu, sg, rowparts, bn_row_parts(D), slot, dr);
-  };
-  if (drop) launch(*drop);
-  else launch(NoDrop{});
-  MOLCLR_LAUNCHED();
-  return MOLCLR_OK;
-}
-
-// The backward of the eval forward (running statistics saved per segment):
-// k_bn_bwd_frozen, then k_bn_bwd_final for dgamma / dbeta.  bn_bwd's
-// arguments, plan and workspace layout; a segment of one row is legal.
-template <typename St>
-int bn_bwd_frozen(const void* dyv, const void* zv, const float* gamma, const float* beta,
-                  const float* save_mean, const float* save_invstd, void* dzv, float* dgamma,
-                  float* dbeta, int nseg, const int64_t* seg_rows, int64_t D, int relu,
-                  int accumulate, void* workspace, size_t workspace_bytes, hipStream_t s,
-                  float* rowparts = nullptr, float* slot = nullptr, const int64_t* drows = nullptr,
-                  int64_t cap = 0, const DropArgs* drop = nullptr) {
-  Segs sg;
-  int64_t P = 0, rows = 0;
-  if (int rc = make_segs(nseg, seg_rows, drows, cap, D, sg, P, rows)) return rc;
-  MOLCLR_REQUIRE(rows > 0 && dyv && zv && save_mean && save_invstd && dzv,
-                 "batchnorm_bwd_frozen: bad args");
-  for (int q = 0; q < nseg && !drows; ++q)
-    MOLCLR_REQUIRE(seg_rows[q] > 0, "batchnorm_bwd_frozen: empty segment");
-  MOLCLR_REQUIRE_WS(workspace_bytes, bn_ws_bytes(P, D, nseg));
-  MOLCLR_REQUIRE(!rowparts || rows < (1ll << 31), "batchnorm_seg_bwd_frozen_max: too many rows");
-  const auto* dy = static_cast<const typename St::T*>(dyv);
-  const auto* z = static_cast<const typename St::T*>(zv);
-  auto* dz = static_cast<typename St::T*>(dzv);
-  const molclr::Band b = molclr::make_band(D);
-  molclr::Workspace w(workspace, workspace_bytes);
-  float* p1 = w.take<float>(P * D);
-  float* p2 = w.take<float>(P * D);
-  w.take<float>(P);
-  w.take<float>(nseg * D);  // scale
-  w.take<float>(nseg * D);  // shift
-  float* k1 = w.take<float>(nseg * D);
-  float* k2 = w.take<float>(nseg * D);
-  const size_t lds = 2 * (size_t)b.band * b.d4 * sizeof(float4);
-  auto launch = [&](auto dr) {
-    using DR = decltype(dr);
-    auto go = [&](auto kernel, int threads) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)P), dim3(threads), lds, s, dy, z,
-                         (const float4*)save_mean, (const float4*)save_invstd, gamma, beta, dz,
-                         b.d4, b.band, sg, rows, relu, (float4*)p1, (float4*)p2, rowparts,
+                         s, dy, z, mean, invstd, gamma, beta, (const float4*)ws.k1,
+                         (const float4*)ws.k2, dz, total4, (int)(D / 4), relu, sg, rowparts,
                          bn_row_parts(D), slot, dr);
-    };
-    if constexpr (St::kBytes == 4) {
-      if (rowparts) go(k_bn_bwd_frozen<St, 1, true, DR>, b.threads);
-      else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
-    } else {
-      if (D % 8 == 0) go(k_bn_bwd_frozen<St, 2, false, DR>, (b.band * (b.d4 / 2) + 63) / 64 * 64);
-      else go(k_bn_bwd_frozen<St, 1, false, DR>, b.threads);
-    }
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3(molclr::ceil_div(D, kRedCols)),
-                       dim3(kRedCols * kRedLanes), 0, s, p1, p2, sg, D, dgamma, dbeta, k1, k2,
-                       accumulate);
-  };
-  if (drop) launch(*drop);
-  else launch(NoDrop{});
+  });
   MOLCLR_LAUNCHED();
   return MOLCLR_OK;
 }
 
-// dtype dispatch of bn_bwd_frozen (row maxima are fp32 only)
-int bn_bwd_frozen_any(const char* who, const void* dy, const void* z, const float* gamma,
-                      const float* beta, const float* save_mean, const float* save_invstd,
-                      void* dz, float* dgamma, float* dbeta, int nseg, const int64_t* seg_rows,
-                      const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D, int dtype, int relu,
-                      int accumulate, float* rowmax, float* slot, const DropArgs* drop,
-                      void* workspace, size_t workspace_bytes, hipStream_t s) {
-  MOLCLR_REQUIRE(!rowmax || dtype == MOLCLR_DTYPE_F32, "%s: row maxima are fp32 only", who);
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_bwd_frozen<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta,
-                                nseg, seg_rows, D, relu, accumulate, workspace, workspace_bytes, s,
-                                rowmax, slot, seg_rows_dev, rows_cap, drop);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "%s: dtype %d", who, dtype);
-  return bn_bwd_frozen<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                               seg_rows, D, relu, accumulate, workspace, workspace_bytes, s,
-                               nullptr, nullptr, seg_rows_dev, rows_cap, drop);
+// what every entry point's BnSegs shares: host-sized segments, no dropout
+BnSegs host_segs(const char* who, int nseg, const int64_t* seg_rows, int64_t D, int dtype,
+                 void* workspace, size_t workspace_bytes, molclr_stream_t stream) {
+  return {who, nseg, seg_rows, nullptr, 0, D, dtype, workspace, workspace_bytes,
+          molclr::as_stream(stream), nullptr};
+}
+// device-sized ones: seg_rows_dev [nseg] on the device, rows_cap rows in all
+BnSegs dev_segs(const char* who, int nseg, const int64_t* seg_rows_dev, int64_t rows_cap,
+                int64_t D, int dtype, void* workspace, size_t workspace_bytes,
+                molclr_stream_t stream) {
+  return {who, nseg, nullptr, seg_rows_dev, rows_cap, D, dtype, workspace, workspace_bytes,
+          molclr::as_stream(stream), nullptr};
 }
 
 }  // namespace
+
+int molclr::bn_forward(const BnFwdArgs& a) {
+  return with_storage(a.dtype, a.who, [&](auto st) { return bn_forward_t<decltype(st)>(a); });
+}
+
+int molclr::bn_backward(const BnBwdArgs& a) {
+  MOLCLR_REQUIRE(!a.rowmax || a.dtype == MOLCLR_DTYPE_F32, "%s: row maxima are fp32 only", a.who);
+  return with_storage(a.dtype, a.who, [&](auto st) { return bn_backward_t<decltype(st)>(a); });
+}
 
 // Workspace that covers any split of `rows` rows into <= MOLCLR_MAX_SEGMENTS
 // segments (the encoder executors size their scratch before knowing it).
@@ -1307,15 +1277,16 @@ size_t molclr_batchnorm_ws_bound(int64_t rows, int64_t D) {
 
 MOLCLR_API size_t molclr_batchnorm_seg_workspace_bytes(int nseg, const int64_t* seg_rows,
                                                        int64_t D) {
-  Segs sg;
-  int64_t P = 0, rows = 0;
-  if (!seg_rows || make_segs(nseg, seg_rows, nullptr, 0, D, sg, P, rows)) return 0;
-  return bn_ws_bytes(P, D, nseg);
+  BnPlan p;
+  if (!seg_rows || make_plan(nseg, seg_rows, nullptr, 0, D, p)) return 0;
+  return bn_ws_bytes(p.P, D, nseg);
 }
 
 MOLCLR_API size_t molclr_batchnorm_workspace_bytes(int64_t rows, int64_t D) {
   return molclr_batchnorm_seg_workspace_bytes(1, &rows, D);
 }
+
+MOLCLR_API int molclr_bn_row_parts(int64_t dim) { return bn_row_parts(dim); }
 
 MOLCLR_API int molclr_batchnorm_seg_fwd(const void* z, const float* gamma, const float* beta,
                                         float* running_mean, float* running_var,
@@ -1324,15 +1295,10 @@ MOLCLR_API int molclr_batchnorm_seg_fwd(const void* z, const float* gamma, const
                                         int64_t D, int dtype, double momentum, double eps,
                                         int training, int relu, void* workspace,
                                         size_t workspace_bytes, molclr_stream_t stream) {
-  hipStream_t s = molclr::as_stream(stream);
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_fwd<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                         save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
-                         workspace, workspace_bytes, s);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_fwd: dtype %d", dtype);
-  return bn_fwd<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                        save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
-                        workspace, workspace_bytes, s);
+  return molclr::bn_forward({host_segs("batchnorm_seg_fwd", nseg, seg_rows, D, dtype, workspace,
+                                       workspace_bytes, stream),
+                             z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
+                             save_mean, save_invstd, nullptr, momentum, eps, training, relu});
 }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd(const void* dy, const void* z, const float* gamma,
@@ -1341,16 +1307,11 @@ MOLCLR_API int molclr_batchnorm_seg_bwd(const void* dy, const void* z, const flo
                                         float* dbeta, int nseg, const int64_t* seg_rows, int64_t D,
                                         int dtype, int relu, int accumulate, void* workspace,
                                         size_t workspace_bytes, molclr_stream_t stream) {
-  hipStream_t s = molclr::as_stream(stream);
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_bwd<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                         seg_rows, D, relu, accumulate, workspace, workspace_bytes, s);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_bwd: dtype %d", dtype);
-  return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                        seg_rows, D, relu, accumulate, workspace, workspace_bytes, s);
+  return molclr::bn_backward({host_segs("batchnorm_seg_bwd", nseg, seg_rows, D, dtype, workspace,
+                                        workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, nullptr, nullptr, 0});
 }
-
-MOLCLR_API int molclr_bn_row_parts(int64_t dim) { return bn_row_parts(dim); }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd_max(const float* dy, const float* z, const float* gamma,
                                             const float* beta, const float* save_mean,
@@ -1360,9 +1321,10 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_max(const float* dy, const float* z, con
                                             float* slot, void* workspace, size_t workspace_bytes,
                                             molclr_stream_t stream) {
   MOLCLR_REQUIRE(rowmax, "batchnorm_seg_bwd_max: null rowmax");
-  return bn_bwd<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                       seg_rows, D, relu, accumulate, workspace, workspace_bytes,
-                       molclr::as_stream(stream), rowmax, slot);
+  return molclr::bn_backward({host_segs("batchnorm_seg_bwd_max", nseg, seg_rows, D,
+                                        MOLCLR_DTYPE_F32, workspace, workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, rowmax, slot, 0});
 }
 
 // Device-sized segments (a captured training step over padded buffers):
@@ -1385,15 +1347,10 @@ MOLCLR_API int molclr_batchnorm_seg_fwd_dev(const void* z, const float* gamma, c
                                             int training, int relu, void* workspace,
                                             size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_REQUIRE(seg_rows_dev, "batchnorm_seg_fwd_dev: null seg_rows_dev");
-  hipStream_t s = molclr::as_stream(stream);
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_fwd<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                         save_mean, save_invstd, nseg, nullptr, D, momentum, eps, training, relu,
-                         workspace, workspace_bytes, s, seg_rows_dev, rows_cap);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_fwd_dev: dtype %d", dtype);
-  return bn_fwd<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                        save_mean, save_invstd, nseg, nullptr, D, momentum, eps, training, relu,
-                        workspace, workspace_bytes, s, seg_rows_dev, rows_cap);
+  return molclr::bn_forward({dev_segs("batchnorm_seg_fwd_dev", nseg, seg_rows_dev, rows_cap, D,
+                                      dtype, workspace, workspace_bytes, stream),
+                             z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
+                             save_mean, save_invstd, nullptr, momentum, eps, training, relu});
 }
 
 // The forward without the apply (molclr_gine_aggregate_bn_fwd applies the
@@ -1408,16 +1365,10 @@ MOLCLR_API int molclr_batchnorm_seg_coeffs(const void* z, const float* gamma, co
                                            void* workspace, size_t workspace_bytes,
                                            molclr_stream_t stream) {
   MOLCLR_REQUIRE(coeffs, "batchnorm_seg_coeffs: null coeffs");
-  hipStream_t s = molclr::as_stream(stream);
-  BnPlan plan;
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_fwd_coeffs<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
-                                save_mean, save_invstd, coeffs, nseg, seg_rows, D, momentum, eps,
-                                training, workspace, workspace_bytes, s, nullptr, 0, plan);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_coeffs: dtype %d", dtype);
-  return bn_fwd_coeffs<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
-                               save_mean, save_invstd, coeffs, nseg, seg_rows, D, momentum, eps,
-                               training, workspace, workspace_bytes, s, nullptr, 0, plan);
+  return molclr::bn_forward({host_segs("batchnorm_seg_coeffs", nseg, seg_rows, D, dtype, workspace,
+                                       workspace_bytes, stream),
+                             z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                             nullptr, save_mean, save_invstd, coeffs, momentum, eps, training, 0});
 }
 
 MOLCLR_API int molclr_batchnorm_seg_coeffs_dev(const void* z, const float* gamma, const float* beta,
@@ -1429,18 +1380,10 @@ MOLCLR_API int molclr_batchnorm_seg_coeffs_dev(const void* z, const float* gamma
                                                int training, void* workspace,
                                                size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_REQUIRE(coeffs && seg_rows_dev, "batchnorm_seg_coeffs_dev: null coeffs / seg_rows_dev");
-  hipStream_t s = molclr::as_stream(stream);
-  BnPlan plan;
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_fwd_coeffs<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
-                                save_mean, save_invstd, coeffs, nseg, nullptr, D, momentum, eps,
-                                training, workspace, workspace_bytes, s, seg_rows_dev, rows_cap,
-                                plan);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_coeffs_dev: dtype %d", dtype);
-  return bn_fwd_coeffs<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked,
-                               save_mean, save_invstd, coeffs, nseg, nullptr, D, momentum, eps,
-                               training, workspace, workspace_bytes, s, seg_rows_dev, rows_cap,
-                               plan);
+  return molclr::bn_forward({dev_segs("batchnorm_seg_coeffs_dev", nseg, seg_rows_dev, rows_cap, D,
+                                      dtype, workspace, workspace_bytes, stream),
+                             z, gamma, beta, running_mean, running_var, num_batches_tracked,
+                             nullptr, save_mean, save_invstd, coeffs, momentum, eps, training, 0});
 }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd_dev(const void* dy, const void* z, const float* gamma,
@@ -1452,55 +1395,10 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_dev(const void* dy, const void* z, const
                                             void* workspace, size_t workspace_bytes,
                                             molclr_stream_t stream) {
   MOLCLR_REQUIRE(seg_rows_dev, "batchnorm_seg_bwd_dev: null seg_rows_dev");
-  MOLCLR_REQUIRE(!rowmax || dtype == MOLCLR_DTYPE_F32, "batchnorm_seg_bwd_dev: row maxima are fp32 only");
-  hipStream_t s = molclr::as_stream(stream);
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_bwd<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                         nullptr, D, relu, accumulate, workspace, workspace_bytes, s, rowmax, slot,
-                         seg_rows_dev, rows_cap);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_bwd_dev: dtype %d", dtype);
-  return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                        nullptr, D, relu, accumulate, workspace, workspace_bytes, s, nullptr,
-                        nullptr, seg_rows_dev, rows_cap);
-}
-
-// The encoder executors' BatchNorm with dropout after it (dropout.h): the
-// entry points above -- host-sized segments (seg_rows) or device-sized ones
-// (seg_rows_dev, rows_cap rows) -- with the mask applied where the ReLU is.
-int molclr::batchnorm_seg_fwd_drop(const void* z, const float* gamma, const float* beta,
-                                   float* running_mean, float* running_var,
-                                   int64_t* num_batches_tracked, void* y, float* save_mean,
-                                   float* save_invstd, int nseg, const int64_t* seg_rows,
-                                   const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D,
-                                   int dtype, double momentum, double eps, int training, int relu,
-                                   const DropArgs& drop, void* workspace, size_t workspace_bytes,
-                                   hipStream_t s) {
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_fwd<StF32>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                         save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
-                         workspace, workspace_bytes, s, seg_rows_dev, rows_cap, &drop);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_fwd_drop: dtype %d", dtype);
-  return bn_fwd<StBF16>(z, gamma, beta, running_mean, running_var, num_batches_tracked, y,
-                        save_mean, save_invstd, nseg, seg_rows, D, momentum, eps, training, relu,
-                        workspace, workspace_bytes, s, seg_rows_dev, rows_cap, &drop);
-}
-
-int molclr::batchnorm_seg_bwd_drop(const void* dy, const void* z, const float* gamma,
-                                   const float* beta, const float* save_mean,
-                                   const float* save_invstd, void* dz, float* dgamma, float* dbeta,
-                                   int nseg, const int64_t* seg_rows, const int64_t* seg_rows_dev,
-                                   int64_t rows_cap, int64_t D, int dtype, int relu, int accumulate,
-                                   float* rowmax, float* slot, const DropArgs& drop,
-                                   void* workspace, size_t workspace_bytes, hipStream_t s) {
-  MOLCLR_REQUIRE(!rowmax || dtype == MOLCLR_DTYPE_F32, "batchnorm_seg_bwd_drop: row maxima are fp32 only");
-  if (dtype == MOLCLR_DTYPE_F32)
-    return bn_bwd<StF32>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                         seg_rows, D, relu, accumulate, workspace, workspace_bytes, s, rowmax, slot,
-                         seg_rows_dev, rows_cap, &drop);
-  MOLCLR_REQUIRE(dtype == MOLCLR_DTYPE_BF16, "batchnorm_seg_bwd_drop: dtype %d", dtype);
-  return bn_bwd<StBF16>(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, nseg,
-                        seg_rows, D, relu, accumulate, workspace, workspace_bytes, s, nullptr,
-                        nullptr, seg_rows_dev, rows_cap, &drop);
+  return molclr::bn_backward({dev_segs("batchnorm_seg_bwd_dev", nseg, seg_rows_dev, rows_cap, D,
+                                       dtype, workspace, workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, rowmax, slot, 0});
 }
 
 // Backward through frozen statistics: save_mean / save_invstd are the ones an
@@ -1513,10 +1411,10 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_frozen(const void* dy, const void* z, co
                                                int64_t D, int dtype, int relu, int accumulate,
                                                void* workspace, size_t workspace_bytes,
                                                molclr_stream_t stream) {
-  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen", dy, z, gamma, beta, save_mean, save_invstd,
-                           dz, dgamma, dbeta, nseg, seg_rows, nullptr, 0, D, dtype, relu,
-                           accumulate, nullptr, nullptr, nullptr, workspace, workspace_bytes,
-                           molclr::as_stream(stream));
+  return molclr::bn_backward({host_segs("batchnorm_seg_bwd_frozen", nseg, seg_rows, D, dtype,
+                                        workspace, workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, nullptr, nullptr, 1});
 }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_max(const float* dy, const float* z,
@@ -1528,10 +1426,10 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_max(const float* dy, const float*
                                                    void* workspace, size_t workspace_bytes,
                                                    molclr_stream_t stream) {
   MOLCLR_REQUIRE(rowmax, "batchnorm_seg_bwd_frozen_max: null rowmax");
-  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen_max", dy, z, gamma, beta, save_mean,
-                           save_invstd, dz, dgamma, dbeta, nseg, seg_rows, nullptr, 0, D,
-                           MOLCLR_DTYPE_F32, relu, accumulate, rowmax, slot, nullptr, workspace,
-                           workspace_bytes, molclr::as_stream(stream));
+  return molclr::bn_backward({host_segs("batchnorm_seg_bwd_frozen_max", nseg, seg_rows, D,
+                                        MOLCLR_DTYPE_F32, workspace, workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, rowmax, slot, 1});
 }
 
 MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_dev(const void* dy, const void* z, const float* gamma,
@@ -1543,37 +1441,13 @@ MOLCLR_API int molclr_batchnorm_seg_bwd_frozen_dev(const void* dy, const void* z
                                                    float* rowmax, float* slot, void* workspace,
                                                    size_t workspace_bytes, molclr_stream_t stream) {
   MOLCLR_REQUIRE(seg_rows_dev, "batchnorm_seg_bwd_frozen_dev: null seg_rows_dev");
-  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen_dev", dy, z, gamma, beta, save_mean,
-                           save_invstd, dz, dgamma, dbeta, nseg, nullptr, seg_rows_dev, rows_cap, D,
-                           dtype, relu, accumulate, rowmax, slot, nullptr, workspace,
-                           workspace_bytes, molclr::as_stream(stream));
+  return molclr::bn_backward({dev_segs("batchnorm_seg_bwd_frozen_dev", nseg, seg_rows_dev,
+                                       rows_cap, D, dtype, workspace, workspace_bytes, stream),
+                              dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta, relu,
+                              accumulate, rowmax, slot, 1});
 }
 
-MOLCLR_API int molclr_batchnorm_bwd_frozen(const float* dy, const float* z, const float* gamma,
-                                           const float* beta, const float* save_mean,
-                                           const float* save_invstd, float* dz, float* dgamma,
-                                           float* dbeta, int64_t rows, int64_t D, int relu,
-                                           int accumulate, void* workspace, size_t workspace_bytes,
-                                           molclr_stream_t stream) {
-  return molclr_batchnorm_seg_bwd_frozen(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma,
-                                         dbeta, 1, &rows, D, MOLCLR_DTYPE_F32, relu, accumulate,
-                                         workspace, workspace_bytes, stream);
-}
-
-// the encoder executors' form: host- or device-sized segments, dropout or none
-int molclr::batchnorm_seg_bwd_frozen_drop(const void* dy, const void* z, const float* gamma,
-                                          const float* beta, const float* save_mean,
-                                          const float* save_invstd, void* dz, float* dgamma,
-                                          float* dbeta, int nseg, const int64_t* seg_rows,
-                                          const int64_t* seg_rows_dev, int64_t rows_cap, int64_t D,
-                                          int dtype, int relu, int accumulate, float* rowmax,
-                                          float* slot, const DropArgs* drop, void* workspace,
-                                          size_t workspace_bytes, hipStream_t s) {
-  return bn_bwd_frozen_any("batchnorm_seg_bwd_frozen", dy, z, gamma, beta, save_mean, save_invstd,
-                           dz, dgamma, dbeta, nseg, seg_rows, seg_rows_dev, rows_cap, D, dtype,
-                           relu, accumulate, rowmax, slot, drop, workspace, workspace_bytes, s);
-}
-
+// the one-segment fp32 forms
 MOLCLR_API int molclr_batchnorm_fwd(const float* z, const float* gamma, const float* beta,
                                     float* running_mean, float* running_var,
                                     int64_t* num_batches_tracked, float* y,
@@ -1595,6 +1469,17 @@ MOLCLR_API int molclr_batchnorm_bwd(const float* dy, const float* z, const float
   return molclr_batchnorm_seg_bwd(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma, dbeta,
                                   1, &rows, D, MOLCLR_DTYPE_F32, relu, accumulate, workspace,
                                   workspace_bytes, stream);
+}
+
+MOLCLR_API int molclr_batchnorm_bwd_frozen(const float* dy, const float* z, const float* gamma,
+                                           const float* beta, const float* save_mean,
+                                           const float* save_invstd, float* dz, float* dgamma,
+                                           float* dbeta, int64_t rows, int64_t D, int relu,
+                                           int accumulate, void* workspace, size_t workspace_bytes,
+                                           molclr_stream_t stream) {
+  return molclr_batchnorm_seg_bwd_frozen(dy, z, gamma, beta, save_mean, save_invstd, dz, dgamma,
+                                         dbeta, 1, &rows, D, MOLCLR_DTYPE_F32, relu, accumulate,
+                                         workspace, workspace_bytes, stream);
 }
 
 MOLCLR_API int molclr_segment_pool_fwd(const float* h, const int32_t* graph_ptr, float* out,

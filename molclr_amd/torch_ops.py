@@ -656,13 +656,8 @@ def _(z, gamma, beta, running_mean, running_var, num_batches_tracked, seg_rows, 
             z.new_empty(() if num_batches_tracked is not None else (0,), dtype=torch.long))
 
 
-@custom_op("molclr::batch_norm_seg_bwd", mutates_args=(), device_types="cuda")
-def batch_norm_seg_bwd(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Tensor,
-                       beta: torch.Tensor, save_mean: torch.Tensor, save_invstd: torch.Tensor,
-                       seg_rows: list[int], relu: bool
-                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(dz, dgamma, dbeta) of batch_norm_seg in training mode (dgamma / dbeta
-    summed over the segments in segment order)."""
+def _bn_seg_bwd(entry, dy, z, gamma, beta, save_mean, save_invstd, seg_rows, relu):
+    """(dz, dgamma, dbeta) from ``entry``: molclr_batchnorm_seg_bwd or _bwd_frozen."""
     _cuda(dy, z, gamma, beta, save_mean, save_invstd)
     z = z.contiguous()
     dy = dy.contiguous().to(z.dtype)
@@ -675,11 +670,21 @@ def batch_norm_seg_bwd(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Tensor,
     dg, dbt = torch.empty(D, **f32), torch.empty(D, **f32)
     wsb = _lib.query("molclr_batchnorm_seg_workspace_bytes", S, c_rows, D)
     ws = ops._ws(wsb, z.device)
-    _lib.call("molclr_batchnorm_seg_bwd", dy.data_ptr(), z.data_ptr(), gamma.data_ptr(),
-              beta.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(),
-              dg.data_ptr(), dbt.data_ptr(), S, c_rows, D, dt, int(bool(relu)), 0, ws.data_ptr(),
-              wsb, _stream(z))
+    _lib.call(entry, dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+              save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(), dg.data_ptr(),
+              dbt.data_ptr(), S, c_rows, D, dt, int(bool(relu)), 0, ws.data_ptr(), wsb, _stream(z))
     return dz, dg, dbt
+
+
+@custom_op("molclr::batch_norm_seg_bwd", mutates_args=(), device_types="cuda")
+def batch_norm_seg_bwd(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Tensor,
+                       beta: torch.Tensor, save_mean: torch.Tensor, save_invstd: torch.Tensor,
+                       seg_rows: list[int], relu: bool
+                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dz, dgamma, dbeta) of batch_norm_seg in training mode (dgamma / dbeta
+    summed over the segments in segment order)."""
+    return _bn_seg_bwd("molclr_batchnorm_seg_bwd", dy, z, gamma, beta, save_mean, save_invstd,
+                       seg_rows, relu)
 
 
 @batch_norm_seg_bwd.register_fake
@@ -696,23 +701,8 @@ def batch_norm_seg_bwd_frozen(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Te
     """(dz, dgamma, dbeta) of batch_norm_seg in eval mode: save_mean /
     save_invstd are the running statistics its forward saved, dz = gamma *
     invstd * dy behind the ReLU mask (molclr_batchnorm_seg_bwd_frozen)."""
-    _cuda(dy, z, gamma, beta, save_mean, save_invstd)
-    z = z.contiguous()
-    dy = dy.contiguous().to(z.dtype)
-    N, D = z.shape
-    rows, c_rows = _seg_rows_arg(seg_rows, N)
-    S = len(rows)
-    dt = _bn_dtype(z)
-    dz = torch.empty_like(z)
-    f32 = dict(dtype=torch.float32, device=z.device)
-    dg, dbt = torch.empty(D, **f32), torch.empty(D, **f32)
-    wsb = _lib.query("molclr_batchnorm_seg_workspace_bytes", S, c_rows, D)
-    ws = ops._ws(wsb, z.device)
-    _lib.call("molclr_batchnorm_seg_bwd_frozen", dy.data_ptr(), z.data_ptr(), gamma.data_ptr(),
-              beta.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(),
-              dg.data_ptr(), dbt.data_ptr(), S, c_rows, D, dt, int(bool(relu)), 0, ws.data_ptr(),
-              wsb, _stream(z))
-    return dz, dg, dbt
+    return _bn_seg_bwd("molclr_batchnorm_seg_bwd_frozen", dy, z, gamma, beta, save_mean, save_invstd,
+                       seg_rows, relu)
 
 
 @batch_norm_seg_bwd_frozen.register_fake

@@ -330,3 +330,46 @@ def test_ops_batch_norm_eval_backward(dev):
     assert torch.allclose(bn.bias.grad.cpu().double(), ref.bias.grad, rtol=1e-5, atol=1e-5)
     after = (bn.running_mean, bn.running_var, bn.num_batches_tracked)
     assert all(torch.equal(a, b) for a, b in zip(before, after))
+
+
+@gpu
+def test_workspace_one_byte_short_is_refused(dev):
+    """The forward, the backward and the frozen backward, each with real
+    tensors and a workspace one byte below the query's answer: every one
+    returns MOLCLR_ERR_WORKSPACE and leaves its outputs, prefilled with a
+    sentinel, untouched."""
+    lib = _lib.load()
+    rows, D = (37, 61), 12
+    N, S = sum(rows), len(rows)
+    z, dy, gamma, beta, mean, invstd, _ = make_case(rows, D, 1, False, 5)
+    zd, dyd = torch.from_numpy(z).to(dev), torch.from_numpy(dy).to(dev)
+    gd, bd = torch.from_numpy(gamma).to(dev), torch.from_numpy(beta).to(dev)
+    md, sd = torch.from_numpy(mean).to(dev), torch.from_numpy(invstd).to(dev)
+    c_rows = (ctypes.c_int64 * S)(*rows)
+    wsb = int(lib.molclr_batchnorm_seg_workspace_bytes(S, c_rows, D))
+    assert wsb > 1
+    ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+
+    def sent(*shape, dtype=torch.float32):
+        return torch.full(shape, int(SENT) if dtype == torch.long else SENT, dtype=dtype,
+                          device=dev)
+
+    y, smean, sinv, rmean, rvar = sent(N, D), sent(S, D), sent(S, D), sent(D), sent(D)
+    nbt = sent(1, dtype=torch.long)
+    rc = lib.molclr_batchnorm_seg_fwd(zd.data_ptr(), gd.data_ptr(), bd.data_ptr(),
+                                      rmean.data_ptr(), rvar.data_ptr(), nbt.data_ptr(),
+                                      y.data_ptr(), smean.data_ptr(), sinv.data_ptr(), S, c_rows,
+                                      D, _lib.DTYPE_F32, 0.1, 1e-5, 1, 1, ws.data_ptr(), wsb - 1,
+                                      None)
+    assert rc == -2, (rc, lib.molclr_last_error())  # MOLCLR_ERR_WORKSPACE
+    outs = [y, smean, sinv, rmean, rvar, nbt]
+    for entry in ("molclr_batchnorm_seg_bwd", "molclr_batchnorm_seg_bwd_frozen"):
+        dz, dg, db = sent(N, D), sent(D), sent(D)
+        rc = getattr(lib, entry)(dyd.data_ptr(), zd.data_ptr(), gd.data_ptr(), bd.data_ptr(),
+                                 md.data_ptr(), sd.data_ptr(), dz.data_ptr(), dg.data_ptr(),
+                                 db.data_ptr(), S, c_rows, D, _lib.DTYPE_F32, 1, 0, ws.data_ptr(),
+                                 wsb - 1, None)
+        assert rc == -2, (entry, rc, lib.molclr_last_error())
+        outs += [dz, dg, db]
+    torch.cuda.synchronize()
+    assert all(bool((t == int(SENT)).all().item()) for t in outs), "a refused call wrote an output"
