@@ -1473,6 +1473,35 @@ int molclr_stage_motif_ids(const int64_t* motif_ptr, const int64_t* motif_ids, i
                            int32_t* status, void* workspace, size_t workspace_bytes,
                            molclr_stream_t stream);
 
+/* ---- Retrieval: exact top-k inner-product search (no reference counterpart;
+ * the nearest-neighbour analysis of the MolCLR paper) -----------------------
+ * For every query row i of q [nq, C] (fp32, row stride ldq) the k best rows
+ * of db [n, C] (fp32, or bf16 with db_is_bf16 != 0; row stride lddb), without
+ * an [nq, n] score matrix in memory: the database is read once per block of
+ * 32 queries and k candidates per query stay on chip.
+ *   Score: score(i, j) = sum_c q[i][c] * db[j][c], accumulated in fp32 (bf16
+ *     values widened exactly).  The summation order of a (query, row) pair
+ *     depends on C alone -- not on n, nq, k, idx_base, the pair's position or
+ *     the grid -- so the top-k of a sharded database merges exactly.
+ *   Order: higher score first, equal scores by lower index; -0.0 equals +0.0
+ *     (reported as +0.0); a NaN score ranks, and is reported, as -inf.
+ *   Output: row i of scores / idx [nq, k] holds the k best rows under that
+ *     order, sorted by it; indices are j + idx_base.  Row j is skipped for
+ *     query i when exclude != NULL and exclude[i] == j + idx_base (the query
+ *     is itself in the library).  With fewer than k rows left the remaining
+ *     entries are score = -inf, idx = -1.
+ *   Limits: 1 <= k <= 64; C % 4 == 0, 4 <= C <= 2048; ldq, lddb >= C with q,
+ *     db and every row 16-byte aligned; n, nq >= 0 (0 is a valid call).  All
+ *     row offsets are 64-bit.  A refused argument, a workspace below
+ *     molclr_topk_dot_workspace_bytes included, is MOLCLR_ERR_ARG before any
+ *     HIP call.  The workspace size is non-decreasing in nq and k.
+ *   No floating-point atomics: results are bit-reproducible run to run. */
+size_t molclr_topk_dot_workspace_bytes(int64_t nq, int64_t n, int64_t C, int k);
+int molclr_topk_dot(const float* q, int64_t ldq, const void* db, int64_t lddb, int db_is_bf16,
+                    int64_t nq, int64_t n, int64_t C, int k, const int64_t* exclude,
+                    int64_t idx_base, float* scores, int64_t* idx, void* workspace,
+                    size_t workspace_bytes, molclr_stream_t stream);
+
 /* ---- Benchmark instrumentation (no reference counterpart) -------------------
  * Opt-in kernel timer.  While a kind is enabled, its launches go through
  * hipExtLaunchKernelGGL with a start/stop event pair recorded by the dispatch

@@ -233,6 +233,9 @@ SIGNATURES = {
     "molclr_stage_motif_ids_workspace_bytes": (c_size_t, [_I64, _I64]),
     "molclr_stage_motif_ids": (c_int, [_P, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P,
                                        c_size_t, _P]),
+    "molclr_topk_dot_workspace_bytes": (c_size_t, [_I64, _I64, _I64, c_int]),
+    "molclr_topk_dot": (c_int, [_P, _I64, _P, _I64, c_int, _I64, _I64, _I64, c_int, _P, _I64, _P,
+                                _P, _P, c_size_t, _P]),
     "molclr_ktimer_start": (c_int, [c_int]),
     "molclr_ktimer_read": (c_int, [c_int, _P, _P]),
     "molclr_ktimer_stop": (c_int, []),

@@ -1382,6 +1382,58 @@ def l2_normalize(z, eps: float = 1e-12):
     return _L2Normalize.apply(z, eps)
 
 
+def topk_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` [rows, C] as molclr_topk_dot takes a matrix: C a multiple of 4
+    (zero columns appended), unit column stride, the base and every row
+    16-byte aligned.  ``t`` itself when it already is, else a padded copy --
+    a library searched more than once is laid out once (MoleculeIndex)."""
+    rows, C = t.shape
+    es = t.element_size()
+    Cp = (C + 3) // 4 * 4
+    if (Cp == C and t.stride(1) == 1 and t.stride(0) >= C and t.stride(0) * es % 16 == 0
+            and t.data_ptr() % 16 == 0):
+        return t
+    ld = (Cp * es + 15) // 16 * 16 // es
+    out = torch.zeros((rows, ld), dtype=t.dtype, device=t.device)
+    out[:, :C] = t
+    return out[:, :Cp]
+
+
+def topk_dot(q, db, k: int, exclude=None, idx_base: int = 0):
+    """Exact top-k inner-product search (molclr_topk_dot, include/molclr.h):
+    ``(scores [nq, k] fp32, idx [nq, k] int64)`` of the fp32 queries ``q``
+    [nq, C] against ``db`` [n, C] (fp32 or bf16), rows ranked by higher score,
+    then lower index; ``idx`` counts from ``idx_base``; row ``exclude[i]`` (an
+    int64 device tensor [nq], in ``idx`` terms) is skipped for query ``i``.
+    No autograd.  Runs on the current stream with a torch-allocated
+    workspace, so a call can be captured."""
+    _check(q, db, exclude)
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != db.shape[1]:
+        raise ValueError(f"topk_dot: q {tuple(q.shape)} and db {tuple(db.shape)} must be [nq, C] "
+                         "and [n, C]")
+    if q.dtype != torch.float32:
+        raise TypeError(f"topk_dot: q must be float32, got {q.dtype}")
+    if db.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"topk_dot: db must be float32 or bfloat16, got {db.dtype}")
+    k = int(k)
+    nq, n = int(q.shape[0]), int(db.shape[0])
+    qa, da = topk_rows(q.detach()), topk_rows(db.detach())
+    C = int(qa.shape[1])
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    if exclude is not None:
+        if exclude.dtype != torch.int64 or exclude.shape != (nq,):
+            raise ValueError("topk_dot: exclude must be an int64 tensor [nq]")
+        exclude = _c(exclude)
+    ws_bytes = _wsq("molclr_topk_dot_workspace_bytes", nq, n, C, k)
+    ws = _ws(ws_bytes, q.device)
+    _lib.call("molclr_topk_dot", qa.data_ptr(), int(qa.stride(0)), da.data_ptr(),
+              int(da.stride(0)), int(db.dtype == torch.bfloat16), nq, n, C, k, _lib.ptr(exclude),
+              int(idx_base), scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws_bytes,
+              _stream(q))
+    return scores, idx
+
+
 def nt_xent(zis, zjs, batch_size, temperature, use_cosine_similarity=True, group=None):
     """NTXentLoss.forward(zis, zjs): R = [zjs; zis] (utils/nt_xent.py:48)."""
     _check(zis, zjs)
